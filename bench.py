@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- images/sec of the CLIP ViT-B/16 pseudolabel + prompt-step loop on N MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (RANK /
-WORLD_SIZE in the environment), or plainly as `python bench.py --gpus N`, in which case it re-executes itself under
-torch.distributed.run on 127.0.0.1 (one process per GPU, RCCL = backend "nccl" on device tensors).
+WORLD_SIZE in the environment), or plainly as `python bench.py --gpus N`, in which case it runs itself as a child
+under torch.distributed.run on 127.0.0.1 (one process per GPU, RCCL = backend "nccl" on device tensors).
 
 One "step" is one full pass of the hot path over this rank's pool of synthetic images (BASELINE.json
 configs[1]: Flowers102-shaped CoOp textual-prompt SSL, C = 102 classes, 16 prompt tokens, k = 16,
@@ -16,10 +16,13 @@ ViT-B/16):
   (iv)  ceil(M / (16 * ranks)) CoOp prompt-tuning steps (text tower fwd+bwd over 102 prompts, frozen
         image tower fwd, head, CE, SGD) over the M selected pseudolabeled images.
 Inputs are resident in HBM before the timed region.  Weak scaling: every rank holds --pool images.
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, live HIP-event timing inside the
-library), `cpu_baseline` (the CPU oracle on a bounded sample, rank 0, N = 1 only), `exact` (the fp32 comparison mode:
-images/sec and its pair overlap with the f16 lists on the same pool) and `secondary` (the other BASELINE.json
-configs: VPT step, UPT step, ViT-L/14@336px encode) -- the last two at N = 1 only, outside the timed region.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the line; with
+--dump-outputs DIR it also writes what the last timed step computed (DIR/<name>.npy, see dump_outputs).
+--full adds everything else, measured as before: `roofline` (dominant kernel, live HIP-event timing inside the
+library during the timed steps), `f16_mode_loop` (one more pass without the index guarantee), `cpu_baseline` (the
+CPU oracle on a bounded sample, rank 0, N = 1 only), `exact` (the fp32 comparison mode: images/sec and its pair
+overlap with the f16 lists on the same pool) and `secondary` (the other BASELINE.json configs: VPT step, UPT step,
+ViT-L/14@336px encode) -- the last three at N = 1 only, outside the timed region.
 """
 import argparse
 import ctypes
@@ -27,6 +30,7 @@ import json
 import math
 import os
 import socket
+import subprocess
 import sys
 import time
 
@@ -129,6 +133,7 @@ class Loop:
         self.m_selected = 0
         self.train_steps = 0
         self.last_lists = None
+        self.last_emb = None        # [n_total, embed] f32 pool embeddings of the last pass (the f16 screen's in identical mode)
 
     def tick(self):
         """Stage boundary: the device work of the stage is done when the clock is read (the next stage depends on it anyway)."""
@@ -150,6 +155,7 @@ class Loop:
             self.m.visual.tower.encode_chunks(self.pool, local, 0, a.pool, a.chunk, streams=streams, hilo=stream == "hilo")
             t1 = self.tick()
             emb = gdist.allgather_rows(local, self.n_total, a.pool, tag="pool_embeddings")
+            self.last_emb = emb
             t2 = self.tick()
             scale = self.m.logit_scale.exp().item()
             _, probs, _, am_p = engine.cosine_head(emb, txt, scale)
@@ -200,6 +206,7 @@ class Loop:
             emb = gdist.allgather_rows(local, self.n_total, a.pool, tag="pool_embeddings")
             t2 = self.tick()
             if model is self.m:
+                self.last_emb = emb
                 self.stage["encode_f16"] += t1 - t0
                 self.stage["allgather"] += t2 - t1
             logits, probs, am_l, am_p = engine.cosine_head(emb, txt, model.logit_scale.exp().item())
@@ -711,6 +718,29 @@ def from_files_block(loop, n=1536, chunk=384, procs=None, slots=1):
         shutil.rmtree(d, ignore_errors=True)
 
 
+DUMP_EMB_ROWS = 4096    # pool embedding rows written by --dump-outputs: 8 MB of f32 at ViT-B/16
+
+
+def dump_outputs(loop, out_dir):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy (float32 / float64, ~8 MB in all):
+    the pseudolabel lists (image index, class; float64 holds the indices exactly), the prompt after the step's SGD updates, and a fixed
+    sample of the pool embeddings the pass encoded (every n_total / 4096-th row, their indices beside them).  The inputs are seeded, so two
+    runs with the same arguments, on two builds of the project, can be compared array for array."""
+    os.makedirs(out_dir, exist_ok=True)
+    img, cls = loop.last_lists
+    emb = loop.last_emb
+    rows = np.linspace(0, emb.shape[0] - 1, min(DUMP_EMB_ROWS, emb.shape[0])).round().astype(np.int64)
+    arrays = {
+        "pseudolabel_image_index": np.asarray(img, dtype=np.float64),
+        "pseudolabel_class": np.asarray(cls, dtype=np.float64),
+        "prompt_prefix": loop.model.prefix.detach().float().cpu().numpy(),
+        "pool_embeddings_sample": emb[torch.from_numpy(rows).to(emb.device)].float().cpu().numpy(),
+        "pool_embeddings_sample_rows": rows.astype(np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -750,13 +780,18 @@ def main():
     ap.add_argument("--no-exact", action="store_true", help="skip the fp32 comparison-mode block")
     ap.add_argument("--exact-chunk", type=int, default=880, help="images per launch of the f32 towers (refinement rounds and the exact block): 220 -> 3 182, 440 -> 3 244, 880 -> 3 282 img/s; rows are bit-identical under any chunking")
     ap.add_argument("--no-secondary", action="store_true", help="skip the VPT / UPT / ViT-L/14@336px block")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the live roofline block (GEMM timing events and clock samples "
+                         "during the timed steps), the f16-mode pass, and at N = 1 the exact, secondary and CPU-baseline blocks (--no-* skip those)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64; see dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
-        # plain `python bench.py --gpus N`: become N ranks (one per GPU) under torch.distributed.run on the loopback address
+        # plain `python bench.py --gpus N`: run N ranks (one per GPU) under torch.distributed.run on the loopback address, in a child process
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                  "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:])
+        sys.exit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                                  "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]))
 
     # The bench's synthetic weights sit on the f16 grid, as the weights of every published CLIP checkpoint do (fp16 archives; the reference's CPU path computes in
     # fp32 on those values cast up): the f32 twin then multiplies exactly the numbers the f16 towers hold, as it would with real weights.  GRIP_SYNTHETIC_FP16=0:
@@ -787,8 +822,9 @@ def main():
     loop.t_pl = loop.t_tr = 0.0
     for k in loop.stage:
         loop.stage[k] = 0.0
-    lib.grip_profile_enable(1)
-    sampler = clock_sampler() if rank == 0 else None
+    if args.full:
+        lib.grip_profile_enable(1)
+    sampler = clock_sampler() if rank == 0 and args.full else None
     gdist.barrier()
     torch.cuda.synchronize()
     clock_marker("timed")
@@ -808,7 +844,10 @@ def main():
     if ws > 1:
         torch.distributed.all_reduce(el, op=torch.distributed.ReduceOp.MAX)
     elapsed = el.item()
-    launches, ms, fl = profile_collect(lib)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(loop, args.dump_outputs)
+    if args.full:
+        launches, ms, fl = profile_collect(lib)
     # wall seconds per stage of the timed loop on every rank: where a scaling curve bends is read off these
     stage_names = list(loop.stage)
     mine = torch.tensor([loop.stage[k] for k in stage_names], dtype=torch.float64, device="cpu" if on_host else device)
@@ -823,7 +862,7 @@ def main():
     stages["allgather"]["bytes_received_per_rank"] = gather_bytes * (ws - 1) // max(ws, 1)
     stages["allgather"]["achieved_GBps_per_rank"] = (gather_bytes * (ws - 1) / ws / stages["allgather"]["max_s"] / 1e9) if ws > 1 and stages["allgather"]["max_s"] > 0 else None
     f16_loop = None
-    if args.mode == "identical":
+    if args.full and args.mode == "identical":
         # the same loop once more WITHOUT the guarantee (the f16 towers' own lists), outside the timed region: what the index guarantee costs
         keep = (loop.t_pl, loop.t_tr, loop.m_selected, loop.train_steps, loop.last_lists, loop.refine_stats)
         args.mode = "f16"
@@ -845,7 +884,6 @@ def main():
         if ws > 1:
             gdist.barrier()
         return
-    dom, achieved = dominant(launches, ms, fl)
     images = loop.n_total * args.steps
     seq = int(getattr(loop.coop_tokens, "_grip_seq_len", 77) or 77)
     seq_zs = int(loop.zs_tokens.argmax(-1).max().item()) + 1
@@ -854,8 +892,6 @@ def main():
     f_img_x = F_IMG if os.environ.get("GRIP_LAST_BLOCK_FULL", "0") not in ("", "0") else vit_flops_executed()
     executed = images * f_img_x + args.steps * args.classes * text_flops(seq_zs) * ws \
         + args.steps * loop.train_steps * ws * (args.batch * f_img_x + 2 * args.classes * text_flops(seq))
-    traffic, mfma_util = pmc_entry(dom)
-    peak = PEAK_F32_TFLOPS if dom < 16 else PEAK_F16_TFLOPS       # profiler variant 0 = the exact tower's f32 GEMM
     rs = loop.refine_stats
     if rs is not None:      # the rows the identical pass re-encoded with the f32 tower are work the engine issued on top of the algorithmic count
         executed += args.steps * (rs.get("rows_mid", 0) + rs.get("rows_exact", rs["rows_refined"])) * f_img_x       # (every re-encode of either tier; rows-only last block since r04)
@@ -870,14 +906,14 @@ def main():
         "config": {"workload": "Flowers102-shaped CoOp textual-prompt SSL pseudolabel+prompt-step loop, ViT-B/16 (BASELINE.json configs[1])",
                    "pseudolabel_mode": args.mode,
                    "comparable_to_earlier_rounds": "rounds 1-2 timed the f16 lists (no index guarantee): compare their `value` with `f16_mode_loop.images_per_sec` "
-                                                   "of this line; `value` here is the identical mode (the default of utils.pseudolabel_top_k since round 3)"
+                                                   "of a --full line; `value` here is the identical mode (the default of utils.pseudolabel_top_k since round 3)"
                                                    if args.mode == "identical" else "same path as rounds 1-2",
                    "index_guarantee": ("calibrated bound, audited: every timed pass returns the lists the error-bounded scan CERTIFIES to be the fp32 (exact-mode) "
                                        "scan's provided every row obeys the measured bound of the tier it was left at -- f16 towers screen the pool, the scan marks "
                                        "the rows whose probabilities cannot decide a comparison the lists depend on, more accurate towers (split-f16, then f32) "
                                        "re-encode those, and after certification a hold-out sample of un-refined rows is re-encoded to check the bound "
                                        "(`identical.audit_*`; pseudolabels.refine_scan).  Equality with the exact mode on this very pool is checked in the "
-                                       "`exact` block of this run and asserted in tests/test_gpu_identical.py")
+                                       "`exact` block of a --full run and asserted in tests/test_gpu_identical.py")
                                       if args.mode == "identical" else
                                       "none: f16 lists (boundary items may differ from the fp32 scan's); run with --mode identical for the guarantee",
                    "pool_images_per_gpu": args.pool, "pool_images_total": loop.n_total, "classes": args.classes, "prompt_tokens": args.prefix, "k": args.k,
@@ -909,7 +945,12 @@ def main():
                       f"row of its output is read) and the text tower's {seq_zs} (zero-shot) / {seq} (CoOp) encoded positions (positions after the last "
                       "EOT cannot influence any output), plus every row the refinement tiers re-encode (counted once per re-encode at the same GF; the split-f16 "
                       "tier issues three f16 MFMA products per multiply-add: not counted); results are identical either way",
-        "roofline": {
+    }
+    if args.full:
+        dom, achieved = dominant(launches, ms, fl)
+        traffic, mfma_util = pmc_entry(dom)
+        peak = PEAK_F32_TFLOPS if dom < 16 else PEAK_F16_TFLOPS       # profiler variant 0 = the exact tower's f32 GEMM
+        out["roofline"] = {
             "bound": "mfma", "kernel": kname(dom), "kernel_instantiation": full_kernel_name(dom),
             "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
             "clock_ghz_sustained": clocks["sclk_mhz_mean"] / 1e3 if clocks else None,
@@ -925,9 +966,8 @@ def main():
             "all_gemm": {kname(i): {"launches": int(launches[i]), "ms": round(float(ms[i]), 3),
                                         "tflops": round(float(fl[i] / (ms[i] * 1e-3) / 1e12), 1) if ms[i] > 0 else None}
                          for i in range(N_SLOTS) if launches[i]},
-        },
-    }
-    if ws == 1:
+        }
+    if ws == 1 and args.full:
         if not args.no_exact:
             clock_marker("exact")
             out["exact"] = exact_block(loop, lib)

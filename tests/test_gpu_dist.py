@@ -167,7 +167,7 @@ def test_bench_two_ranks(tmp_path):
     env = dict(_env(tmp_path), GRIP_COMM_TRACE=str(tmp_path / "comm.log"))
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-                          "--pool", "1320", "--chunk", "220"], env=env, capture_output=True, text=True, timeout=1200, cwd=tmp_path)
+                          "--pool", "1320", "--chunk", "220", "--full"], env=env, capture_output=True, text=True, timeout=1200, cwd=tmp_path)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]

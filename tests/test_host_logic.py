@@ -256,6 +256,27 @@ def test_bench_quotes_pmc_traffic_only_for_the_exact_instantiation(tmp_path, mon
     assert bench.pmc_entry(0 * 16 + 3) == (None, None)                  # the f32 GEMM is not in the file
 
 
+def test_bench_dump_outputs_writes_the_last_step_as_float_arrays(tmp_path):
+    """bench.py --dump-outputs: the last step's pseudolabel lists, prompt and a fixed sample of its pool embeddings as float32 / float64 .npy files,
+    within 64 MB; the sampled rows depend on the pool size only."""
+    import types
+
+    import bench
+    n = 10000
+    emb = torch.randn(n, 512)
+    loop = types.SimpleNamespace(last_lists=(np.array([3, 7, 9999]), np.array([1, 0, 101])), last_emb=emb,
+                                 model=types.SimpleNamespace(prefix=torch.nn.Parameter(torch.randn(1, 16, 512))))
+    bench.dump_outputs(loop, str(tmp_path / "out"))
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert set(got) == {"pseudolabel_image_index", "pseudolabel_class", "prompt_prefix", "pool_embeddings_sample", "pool_embeddings_sample_rows"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["pseudolabel_image_index"].tolist() == [3, 7, 9999] and got["pseudolabel_class"].tolist() == [1, 0, 101]
+    rows = got["pool_embeddings_sample_rows"].astype(np.int64)
+    assert len(rows) == bench.DUMP_EMB_ROWS and rows[0] == 0 and rows[-1] == n - 1 and (np.diff(rows) > 0).all()
+    assert np.array_equal(got["pool_embeddings_sample"], emb[rows].numpy())
+    assert np.array_equal(got["prompt_prefix"], loop.model.prefix.detach().numpy())
+
+
 def test_grip_schedule_matches_the_reference_formula():
     """TrainingStrategy._n_pseudoshots against the literal arithmetic of methods/semi_supervised_learning/pseudo_iterative.py:62-75 (first
     iteration) and :113-125 (ALL_UNLABELED growth; identical in the ul / trzsl twins): pseudo-shots per class at GRIP iteration 1 .. num_iter."""

@@ -12,8 +12,8 @@ cd $R
 python tools/clock_trace.py --probe > $OUT/probe.txt 2>&1
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/micro/mfma_peak.hip -o /tmp/mfma_peak || exit 1
 python tools/clock_trace.py --out $OUT/mfma_peak.csv -- /tmp/mfma_peak 4 > $OUT/mfma_peak.json 2> $OUT/mfma_peak.err
-python tools/clock_trace.py --out $OUT/bench_f16.csv -- python bench.py --mode f16 --no-exact --no-secondary --no-cpu-baseline --steps 3 > $OUT/bench_f16.json 2> $OUT/bench_f16.err
-python tools/clock_trace.py --out $OUT/bench_identical.csv -- python bench.py --no-exact --no-secondary --no-cpu-baseline --steps 2 > $OUT/bench_identical.json 2> $OUT/bench_identical.err
+python tools/clock_trace.py --out $OUT/bench_f16.csv -- python bench.py --full --mode f16 --no-exact --no-secondary --no-cpu-baseline --steps 3 > $OUT/bench_f16.json 2> $OUT/bench_f16.err
+python tools/clock_trace.py --out $OUT/bench_identical.csv -- python bench.py --full --no-exact --no-secondary --no-cpu-baseline --steps 2 > $OUT/bench_identical.json 2> $OUT/bench_identical.err
 tail -n 40 $OUT/probe.txt $OUT/mfma_peak.json
 grep -h "TFLOP/s" $OUT/mfma_peak.json $OUT/mfma_peak.err 2>/dev/null
 python - <<'PY'

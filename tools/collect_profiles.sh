@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 if [ "${SKIP_STATS:-0}" != "1" ]; then
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o r -- python $R/bench.py --no-cpu-baseline --no-secondary --no-exact > $OUT/bench_line.json 2> $OUT/bench_stderr.log
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o r -- python $R/bench.py --full --no-cpu-baseline --no-secondary --no-exact > $OUT/bench_line.json 2> $OUT/bench_stderr.log
 cp $(find /tmp/prof_stats -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv
 fi
 # (the PMC passes time ONE pass over a fresh pool, which the auto policy screens with the compensated stream; the timed passes of the default bench screen the
@@ -37,5 +37,5 @@ with open(dst, "w", newline="") as f:
 PY
 done
 unset GRIP_SCREEN_STREAM
-if [ "${FULL_LINE:-1}" = "1" ]; then timeout 900 python $R/bench.py > $OUT/bench_line_full.json 2>> $OUT/bench_stderr.log; fi
+if [ "${FULL_LINE:-1}" = "1" ]; then timeout 900 python $R/bench.py --full > $OUT/bench_line_full.json 2>> $OUT/bench_stderr.log; fi
 ls -la $OUT
