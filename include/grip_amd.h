@@ -38,7 +38,7 @@ typedef enum {
 const char* grip_last_error(void);
 /* ABI version of this header; the host layer refuses a library that reports another one. */
 int grip_abi_version(void);
-#define GRIP_ABI_VERSION 8
+#define GRIP_ABI_VERSION 9
 
 /* ------------------------------------------------------------------------------------------
  * Tower description.  kind 0 = vision transformer (clip_model.visual, wrapped by
@@ -107,20 +107,28 @@ int grip_workspace_bytes(const grip_tower* t, int batch, int n_prefix, int seq_l
  * (models/clip_encoders.py:123-194; :93-102 with n_prefix = 0).
  *   images     [batch, 3, R, R] f32 (images_f16 = 0) or f16 (images_f16 = 1), NCHW
  *   prefix     [n_prefix, width] f32, or NULL when n_prefix == 0; inserted between CLS and the
- *              patches after the positional embedding, shared by the whole batch
+ *              patches after the positional embedding, shared by the whole batch (image_prefix [P, d] / [1, P, d] expanded,
+ *              :148).  With GRIP_FWD_PER_IMAGE_PREFIX: [batch, n_prefix, width] f32, image b's tokens 1 .. n_prefix are prefix[b]
+ *              (image_prefix [B, P, d], one prompt per image).
  *   out_emb    [batch, embed_dim] f32 (un-normalised, as the reference returns it)
  *   flags      GRIP_FWD_TRAIN (= the `train` argument of earlier ABIs: 1 keeps the activations backward needs) and / or
- *              GRIP_FWD_NO_POS_EMB (forward(..., pos_emb=False), :141: CLS and patches without the positional embedding)
+ *              GRIP_FWD_NO_POS_EMB (forward(..., pos_emb=False), :141: CLS and patches without the positional embedding) and / or
+ *              GRIP_FWD_PER_IMAGE_PREFIX (ABI 9: prefix holds one prompt per image, see above; valid with every tower precision and with
+ *              GRIP_FWD_TRAIN, GRIP_FWD_NO_POS_EMB and GRIP_FWD_STREAM_HILO; an error on a text tower, whose per-class contexts are
+ *              prefix_classes = n_class).  Without it every kernel runs exactly as in ABI 8.
  *   generation NULL, or receives the number of this train-mode forward (0 without GRIP_FWD_TRAIN).  Several train-mode forwards may
  *              be outstanding, each on its own workspace; a second one on the SAME workspace overwrites the first one's
- *              saved activations, and a backward that presents the first one's number then fails with GRIP_ERR_STATE.
+ *              saved activations, and a backward that presents the first one's number then fails with GRIP_ERR_STATE.  The train-mode
+ *              state also records GRIP_FWD_PER_IMAGE_PREFIX: it decides the shape of grip_vit_backward_prefix's grad_prefix.
  */
 int grip_vit_forward(grip_tower* t, const void* images, int images_f16, const float* prefix, int n_prefix,
                      int batch, float* out_emb, void* workspace, size_t workspace_bytes, int flags, uint64_t* generation, void* stream);
 
 /* Input-gradient chain of the frozen ViT down to the prompt slice (autograd of the above w.r.t.
  * image_prefix only; no weight gradients exist).  Must follow a train-mode forward on the same
- * workspace, exactly once per forward; generation = the number that forward returned (0 = do not check).  grad_emb [batch, embed_dim] f32 -> grad_prefix [n_prefix, width] f32 (summed over batch). */
+ * workspace, exactly once per forward; generation = the number that forward returned (0 = do not check).  grad_emb [batch, embed_dim] f32 -> grad_prefix [n_prefix, width] f32 (summed over batch).
+ * After a forward with GRIP_FWD_PER_IMAGE_PREFIX: prefix (the same tensor the forward read) and grad_prefix are [batch, n_prefix, width] f32 -- image b's
+ * prompt gradient alone, no sum over the batch (autograd of image_prefix [B, P, d]); bit-reproducible (no atomics, one writer per element). */
 int grip_vit_backward_prefix(grip_tower* t, const float* grad_emb, const float* prefix, float* grad_prefix,
                              void* workspace, size_t workspace_bytes, uint64_t generation, void* stream);
 
@@ -153,6 +161,7 @@ int grip_vit_backward_prefix(grip_tower* t, const float* grad_emb, const float* 
                                   accumulate -- measured: 2.5 - 3x less direction error against the f32 tower for ~2 bytes more traffic per stream element and
                                   residual GEMM.  GEMM operands stay f16 (the hi part).  The SCREEN of the pseudolabel pass (grip_amd.pseudolabels) runs in
                                   this mode; train-mode forwards and every other caller keep the plain f16 stream the reference's GPU path has. */
+#define GRIP_FWD_PER_IMAGE_PREFIX 32 /* grip_vit_forward (ABI 9): prefix is [batch, n_prefix, width], one prompt per image (see grip_vit_forward).  Bit 16 stays unassigned. */
 int grip_text_forward(grip_tower* t, const int32_t* token_ids, const int32_t* eot_index, const float* prefix,
                       int n_prefix, int prefix_classes, int n_class, int seq_len, float* out_emb,
                       void* workspace, size_t workspace_bytes, int flags, uint64_t* generation, void* stream);

@@ -220,7 +220,8 @@ float gemm_split_weight_scale();
 // row-wise kernels (rowops.hip)
 int launch_im2col(const void* images, int images_f16, void* out, int out_f32, int B, int R, int patch, int Kpad, hipStream_t s);
 int launch_vit_assemble_ln(const float* patch_out, const float* cls, const float* pos, const float* prefix, int P,   /* x_lo (last argument, optional): the lo parts of a compensated stream */
-                           const float* gamma, const float* beta, void* x, int f32, float* rowstat, int B, int G2, int d, hipStream_t s, half_t* x_lo = nullptr);
+                           const float* gamma, const float* beta, void* x, int f32, float* rowstat, int B, int G2, int d, hipStream_t s, half_t* x_lo = nullptr,
+                           int per_image = 0);   /* per_image: prefix is [B, P, d] (one prompt per image), else [P, d] shared by the batch */
 // rowstat [M, 2] = (mean, rstd) of every row from the [M, parts, 2] partial sums the residual GEMM epilogues emit
 int launch_ln_stats_finalize(const float* stat_part, int parts, float* rowstat, int M, int d, hipStream_t s);
 // W' = f16(gamma o W) [N, K]; colsum[n] = sum_k W'[n][k]; bias_out[n] = bias[n] + sum_k beta[k] W[n][k]
@@ -278,5 +279,7 @@ int launch_ln_bwd_scatter(const resid_t* x, const float* dy, const int32_t* inde
 int launch_ln_bwd_scatter_fill(const resid_t* x, const float* dy, const int32_t* index, int stride, int first, const float* gamma, float* dx, half_t* dxh,
                                int n, int M, int d, hipStream_t s);
 int launch_vit_prefix_grad(const float* dx, const float* prefix, const float* gamma, const float* scale, float* grad, int B, int S, int P, int d, hipStream_t s);
+// per-image prompts (GRIP_FWD_PER_IMAGE_PREFIX): prefix / grad [B, P, d], no sum over the batch
+int launch_vit_prefix_grad_per_image(const float* dx, const float* prefix, const float* gamma, const float* scale, float* grad, int B, int S, int P, int d, hipStream_t s);
 int launch_text_prefix_grad(const float* dx, const float* scale, float* grad, int C, int T, int P, int prefix_classes, int d, hipStream_t s);
 int launch_grad_scale_cast(const float* g, half_t* g16, float* scale, int n, hipStream_t s);

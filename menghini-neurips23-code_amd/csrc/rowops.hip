@@ -84,12 +84,14 @@ int launch_gather_ln_f16(const void* x, const int32_t* row_index, int row_stride
 // ------------------------------------------------------------------------------------------------
 // Vision sequence assembly + ln_pre  (models/clip_encoders.py:135-163):
 //   row (b, 0)            = class_embedding + pos[0]
-//   row (b, 1..P)         = prefix[s-1]                         (no positional embedding)
+//   row (b, 1..P)         = prefix[b * prefix_stride + (s-1) * d]  (no positional embedding)
 //   row (b, 1+P+j)        = patch_out[b*G2 + j] + pos[1+j]
-// then LayerNorm -> x (residual stream), S = 1 + P + G2.
+// then LayerNorm -> x (residual stream), S = 1 + P + G2.  prefix_stride = 0: one prompt [P, d] shared by the batch (image_prefix
+// [P, d] / [1, P, d] expanded, :148); P * d: one prompt per image ([B, P, d], GRIP_FWD_PER_IMAGE_PREFIX).  Only the address of the
+// prompt rows depends on it: every row's arithmetic is the same in both forms.
 template <int NV, typename RT>
 __global__ __launch_bounds__(256) void vit_assemble_ln_kernel(const float* __restrict__ patch_out, const float* __restrict__ cls,
-                                                              const float* __restrict__ pos, const float* __restrict__ prefix, int P,
+                                                              const float* __restrict__ pos, const float* __restrict__ prefix, int P, int64_t prefix_stride,
                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
                                                               RT* __restrict__ x, float* __restrict__ rowstat, int B, int G2, int d, half_t* __restrict__ x_lo) {
     const int lane = threadIdx.x & 63;
@@ -102,7 +104,7 @@ __global__ __launch_bounds__(256) void vit_assemble_ln_kernel(const float* __res
     const f32x4* src;
     const f32x4* add = nullptr;
     if (s == 0) { src = (const f32x4*)cls; add = (const f32x4*)pos; }     // pos == nullptr: pos_emb=False (models/clip_encoders.py:141)
-    else if (s <= P) { src = (const f32x4*)(prefix + (size_t)(s - 1) * d); }
+    else if (s <= P) { src = (const f32x4*)(prefix + (size_t)b * prefix_stride + (size_t)(s - 1) * d); }
     else { const int j = s - 1 - P; src = (const f32x4*)(patch_out + ((size_t)b * G2 + j) * d); add = pos ? (const f32x4*)(pos + (size_t)(1 + j) * d) : nullptr; }
 #pragma unroll
     for (int i = 0; i < NV; ++i)
@@ -133,12 +135,14 @@ __global__ __launch_bounds__(256) void vit_assemble_ln_kernel(const float* __res
 }
 
 int launch_vit_assemble_ln(const float* patch_out, const float* cls, const float* pos, const float* prefix, int P,
-                           const float* gamma, const float* beta, void* x, int f32, float* rowstat, int B, int G2, int d, hipStream_t s, half_t* x_lo) {
+                           const float* gamma, const float* beta, void* x, int f32, float* rowstat, int B, int G2, int d, hipStream_t s, half_t* x_lo,
+                           int per_image) {
     const int rows = B * (1 + P + G2);
+    const int64_t prefix_stride = per_image ? (int64_t)P * d : 0;
     if (f32) {
-        DISPATCH_NV(d, hipLaunchKernelGGL((vit_assemble_ln_kernel<NV, float>), dim3((rows + 3) / 4), dim3(256), 0, s, patch_out, cls, pos, prefix, P, gamma, beta, (float*)x, rowstat, B, G2, d, (half_t*)nullptr));
+        DISPATCH_NV(d, hipLaunchKernelGGL((vit_assemble_ln_kernel<NV, float>), dim3((rows + 3) / 4), dim3(256), 0, s, patch_out, cls, pos, prefix, P, prefix_stride, gamma, beta, (float*)x, rowstat, B, G2, d, (half_t*)nullptr));
     } else {
-        DISPATCH_NV(d, hipLaunchKernelGGL((vit_assemble_ln_kernel<NV, resid_t>), dim3((rows + 3) / 4), dim3(256), 0, s, patch_out, cls, pos, prefix, P, gamma, beta, (resid_t*)x, rowstat, B, G2, d, x_lo));
+        DISPATCH_NV(d, hipLaunchKernelGGL((vit_assemble_ln_kernel<NV, resid_t>), dim3((rows + 3) / 4), dim3(256), 0, s, patch_out, cls, pos, prefix, P, prefix_stride, gamma, beta, (resid_t*)x, rowstat, B, G2, d, x_lo));
     }
     GRIP_CHECK_HIP(hipGetLastError());
     return GRIP_OK;

@@ -268,6 +268,27 @@ __global__ __launch_bounds__(512) void vit_prefix_grad_kernel(const float* __res
         if (lane + 64 * i < d4) o[lane + 64 * i] = acc[i] * inv;
 }
 
+// Per-image visual prompts (GRIP_FWD_PER_IMAGE_PREFIX): grad_prefix[b, s] = inv_scale * LNbwd(dx[b*S + 1 + s]; prefix[b, s]).  Every (image, token)
+// row is its own prompt's gradient -- nothing is summed over the batch -- so one wave owns one of the B x P rows (four per workgroup: a 16 x 16
+// VPT batch is 64 workgroups spread over the chip, where the shared kernel's P workgroups would loop over the images).  Each output element is
+// written by exactly one lane from the same sequence of f32 operations: the same bits on every run.
+template <int NV>
+__global__ __launch_bounds__(256) void vit_prefix_grad_per_image_kernel(const float* __restrict__ dx, const float* __restrict__ prefix, const float* __restrict__ gamma,
+                                                                        const float* __restrict__ scale, float* __restrict__ grad, int B, int S, int P, int d) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= B * P) return;
+    const int b = row / P, s = row - b * P;
+    const int d4 = d >> 2;
+    f32x4 g[NV];
+    ln_bwd_row<NV>(prefix + (size_t)row * d, (const f32x4*)(dx + ((size_t)b * S + 1 + s) * d), (const f32x4*)gamma, lane, d4, d, g);
+    const float inv = scale[1];
+    f32x4* o = (f32x4*)(grad + (size_t)row * d);
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+        if (lane + 64 * i < d4) o[lane + 64 * i] = g[i] * inv;
+}
+
 // Textual prompt slice: grad_prefix[pc][p] = inv_scale * sum_{c in group} dx[c*T + 1 + p]
 // One wave per (prompt token, 256-float slice of the row): a shared prompt sums C rows in class order, sixteen loads in flight.
 __global__ __launch_bounds__(256) void text_prefix_grad_kernel(const float* __restrict__ dx, const float* __restrict__ scale, float* __restrict__ grad,
@@ -408,6 +429,13 @@ int launch_ln_bwd_scatter_fill(const resid_t* x, const float* dy, const int32_t*
 }
 int launch_vit_prefix_grad(const float* dx, const float* prefix, const float* gamma, const float* scale, float* grad, int B, int S, int P, int d, hipStream_t s) {
     DISPATCH_NV_B(d, hipLaunchKernelGGL(vit_prefix_grad_kernel<NV>, dim3(P), dim3(512), 0, s, dx, prefix, gamma, scale, grad, B, S, P, d));
+    GRIP_CHECK_HIP(hipGetLastError());
+    return GRIP_OK;
+}
+int launch_vit_prefix_grad_per_image(const float* dx, const float* prefix, const float* gamma, const float* scale, float* grad, int B, int S, int P, int d, hipStream_t s) {
+    GRIP_REQUIRE(B > 0 && P > 0 && S >= 1 + P, "vit_prefix_grad_per_image: bad shape (B=%d P=%d S=%d)", B, P, S);
+    const int rows = B * P;
+    DISPATCH_NV_B(d, hipLaunchKernelGGL(vit_prefix_grad_per_image_kernel<NV>, dim3((rows + 3) / 4), dim3(256), 0, s, dx, prefix, gamma, scale, grad, B, S, P, d));
     GRIP_CHECK_HIP(hipGetLastError());
     return GRIP_OK;
 }

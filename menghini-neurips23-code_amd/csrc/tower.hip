@@ -247,6 +247,7 @@ struct grip_tower {
         Workspace w;
         const int32_t* eot = nullptr;
         int prefix_classes = 0;
+        bool per_image = false;    // vision: the forward ran with GRIP_FWD_PER_IMAGE_PREFIX (prefix and its gradient are [batch, n_prefix, width])
         uint64_t generation = 0;
         bool consumed = false;     // its backward has run (the backward works in place on the saved activations: one per forward)
     };
@@ -638,7 +639,8 @@ static int check_ws(grip_tower* t, int batch, int P, int train, void* ws, size_t
 
 // Book-keeping of a finished forward: a train-mode one registers its state under the workspace (replacing whatever
 // forward used that workspace before) and hands out a fresh generation number; an inference one invalidates it.
-static void note_forward(grip_tower* t, void* workspace, int train, const Workspace& w, const int32_t* eot, int prefix_classes, uint64_t* generation) {
+static void note_forward(grip_tower* t, void* workspace, int train, const Workspace& w, const int32_t* eot, int prefix_classes, uint64_t* generation,
+                         bool per_image = false) {
     if (train) {
         // Consumed entries only serve a clearer error message ("already back-propagated"); workspaces that were freed since (pools dropped with a
         // key change, graph pins released per GRIP iteration) would otherwise stay in the map for good, and a recycled address could hit a stale one.
@@ -646,7 +648,7 @@ static void note_forward(grip_tower* t, void* workspace, int train, const Worksp
             for (auto it = t->pending.begin(); it != t->pending.end();)
                 it = (it->second.consumed && it->first != workspace) ? t->pending.erase(it) : std::next(it);
         grip_tower::TrainState& st = t->pending[workspace];
-        st.w = w; st.eot = eot; st.prefix_classes = prefix_classes; st.generation = ++t->generation; st.consumed = false;
+        st.w = w; st.eot = eot; st.prefix_classes = prefix_classes; st.per_image = per_image; st.generation = ++t->generation; st.consumed = false;
         if (generation) *generation = st.generation;
     } else {
         t->pending.erase(workspace);
@@ -658,8 +660,9 @@ extern "C" int grip_vit_forward(grip_tower* t, const void* images, int images_f1
                                 int batch, float* out_emb, void* workspace, size_t workspace_bytes, int flags, uint64_t* generation, void* stream) {
     try {
         GRIP_REQUIRE(t && t->D.kind == 0, "vit_forward: not a vision tower");
-        GRIP_REQUIRE((flags & ~(GRIP_FWD_TRAIN | GRIP_FWD_NO_POS_EMB | GRIP_FWD_STREAM_HILO)) == 0, "vit_forward: unknown flag bits 0x%x", flags);
+        GRIP_REQUIRE((flags & ~(GRIP_FWD_TRAIN | GRIP_FWD_NO_POS_EMB | GRIP_FWD_STREAM_HILO | GRIP_FWD_PER_IMAGE_PREFIX)) == 0, "vit_forward: unknown flag bits 0x%x", flags);
         const int train = flags & GRIP_FWD_TRAIN;
+        const int per_image = (flags & GRIP_FWD_PER_IMAGE_PREFIX) ? 1 : 0;      // prefix [batch, n_prefix, width]: rows (b, 1 .. P) read image b's prompt
         GRIP_REQUIRE(!(flags & GRIP_FWD_STREAM_HILO) || (!train && !t->f32), "vit_forward: GRIP_FWD_STREAM_HILO is an inference mode of the f16 towers");
         GRIP_REQUIRE(images && out_emb && (n_prefix == 0 || prefix), "vit_forward: null pointer");
         Workspace w;
@@ -675,7 +678,7 @@ extern "C" int grip_vit_forward(grip_tower* t, const void* images, int images_f1
         resid_t* x0 = train ? w.x_in[0] : w.x;
         w.hilo = (flags & GRIP_FWD_STREAM_HILO) ? 1 : 0;
         RUN(launch_vit_assemble_ln(w.patch_out, F + t->L.cls, (flags & GRIP_FWD_NO_POS_EMB) ? nullptr : F + t->L.pos, prefix, n_prefix, F + t->L.lnpre_g, F + t->L.lnpre_b, x0, f, (train && !train_fold(t)) ? nullptr : w.rowstat, batch, G2, d, s,
-                                   w.hilo ? w.x_lo : nullptr));
+                                   w.hilo ? w.x_lo : nullptr, per_image));
         resid_t* xf = nullptr;
         bool compact = false;
         RUN(run_blocks(t, w, x0, /*causal=*/0, nullptr, s, &xf, &compact));
@@ -683,7 +686,7 @@ extern "C" int grip_vit_forward(grip_tower* t, const void* images, int images_f1
         a = GemmArgs{};
         a.f32 = f; a.A = w.cls16; a.W = t->wop(t->L.projT); a.M = batch; a.N = D.embed_dim; a.K = d; a.out = out_emb; a.ldc = D.embed_dim;
         RUN(launch_gemm(EPI_F32, a, s));
-        note_forward(t, workspace, train, w, nullptr, 0, generation);
+        note_forward(t, workspace, train, w, nullptr, 0, generation, per_image != 0);
         return GRIP_OK;
     } catch (...) { grip_set_error("vit_forward: exception"); return GRIP_ERR_ARG; }
 }
@@ -694,6 +697,7 @@ extern "C" int grip_text_forward(grip_tower* t, const int32_t* token_ids, const 
     try {
         GRIP_REQUIRE(t && t->D.kind == 1, "text_forward: not a text tower");
         GRIP_REQUIRE(token_ids && eot_index && out_emb && (n_prefix == 0 || prefix), "text_forward: null pointer");
+        GRIP_REQUIRE(!(flags & GRIP_FWD_PER_IMAGE_PREFIX), "text_forward: GRIP_FWD_PER_IMAGE_PREFIX is a vision-tower flag (one context per class: prefix_classes = n_class)");
         GRIP_REQUIRE(n_prefix == 0 || prefix_classes == 1 || prefix_classes == n_class, "text_forward: prefix_classes must be 1 or n_class");
         GRIP_REQUIRE((flags & ~(GRIP_FWD_TRAIN | GRIP_FWD_SHARED_PREFIX | GRIP_FWD_NO_POS_EMB)) == 0, "text_forward: unknown flag bits 0x%x", flags);
         const int train = flags & GRIP_FWD_TRAIN;
@@ -930,7 +934,10 @@ extern "C" int grip_vit_backward_prefix(grip_tower* t, const float* grad_emb, co
         hipStream_t s = (hipStream_t)stream;
         RUN(backward_head_of_tower(t, w, grad_emb, nullptr, s));
         RUN(run_blocks_backward(t, w, 0, nullptr, s));
-        RUN(launch_vit_prefix_grad(w.dx, prefix, t->w32 + t->L.lnpre_g, w.scale, grad_prefix, w.batch, w.S, w.P, t->D.width, s));
+        if (st.per_image)     // one prompt per image: grad_prefix [batch, n_prefix, width], image b's rows only
+            RUN(launch_vit_prefix_grad_per_image(w.dx, prefix, t->w32 + t->L.lnpre_g, w.scale, grad_prefix, w.batch, w.S, w.P, t->D.width, s));
+        else
+            RUN(launch_vit_prefix_grad(w.dx, prefix, t->w32 + t->L.lnpre_g, w.scale, grad_prefix, w.batch, w.S, w.P, t->D.width, s));
         return GRIP_OK;
     } catch (...) { grip_set_error("vit_backward_prefix: exception"); return GRIP_ERR_ARG; }
 }

@@ -169,7 +169,22 @@ class Tower:
         return c_void_p(ws.data_ptr() + off), ws.numel() - off
 
     # ---- forward / backward
+    def vit_prefix(self, prefix, B):
+        """The visual prompt as the native call takes it, following `image_prefix.expand(B, -1, -1)` of the reference
+        (models/clip_encoders.py:148): (prefix f32 contiguous or None, n_prefix, per_image).  [P, d] and [1, P, d] are one prompt shared by the
+        batch (passed as [P, d]); [B, P, d] is one prompt per image (GRIP_FWD_PER_IMAGE_PREFIX); any other leading size raises, as expand does."""
+        if prefix is None:
+            return None, 0, False
+        P = prefix.shape[-2]
+        if prefix.dim() == 3 and prefix.shape[0] != 1:
+            if prefix.shape[0] != B or prefix.shape[2] != self.width:
+                raise native.GripError(f"visual prompt of shape {tuple(prefix.shape)} for a batch of {B} images: expected [P, {self.width}], "
+                                       f"[1, P, {self.width}] (shared) or [{B}, P, {self.width}] (one prompt per image)")
+            return prefix.contiguous().float(), P, True
+        return prefix.reshape(P, self.width).contiguous().float(), P, False
+
     def vit_forward(self, images, prefix=None, train=False, pos_emb=True):
+        """CustomVisionTransformer.forward: images [B, 3, R, R]; prefix None, [P, d] / [1, P, d] (shared) or [B, P, d] (one prompt per image)."""
         if not self._finalized:
             self.finalize()
         assert self.kind == 0
@@ -177,17 +192,16 @@ class Tower:
         if images.dtype not in (torch.float32, torch.float16):
             images = images.float()
         B = images.shape[0]
-        P = 0 if prefix is None else prefix.shape[-2]
-        if prefix is not None:
-            prefix = prefix.reshape(P, self.width).contiguous().float()
+        prefix, P, per_image = self.vit_prefix(prefix, B)
         out = torch.empty(B, self.embed_dim, dtype=torch.float32, device=self.device)
         ws = self.workspace(B, P, train)
         p, n = self._aligned(ws)
         gen = c_uint64(0)
+        flags = (native.FWD_TRAIN if train else 0) | (0 if pos_emb else native.FWD_NO_POS_EMB) | (native.FWD_PER_IMAGE_PREFIX if per_image else 0)
         native.check(self.lib.grip_vit_forward(self.handle, _ptr(images), int(images.dtype == torch.float16), _ptr(prefix), P, B,
-                                               _ptr(out), p, n, (native.FWD_TRAIN if train else 0) | (0 if pos_emb else native.FWD_NO_POS_EMB),
-                                               byref(gen), _stream()))
+                                               _ptr(out), p, n, flags, byref(gen), _stream()))
         ws.generation = gen.value
+        ws.per_image = B if per_image else 0      # the backward's grad_prefix is [B, P, d] then (vit_backward checks it is given that shape)
         return out, ws
 
     @torch.no_grad()
@@ -198,11 +212,17 @@ class Tower:
         a single-stream pass (+6 % on the 50k-image pass).  streams=1 keeps everything on the current stream (per-kernel
         timings are only meaningful that way).  `images` is a tensor or a callable (a, b) -> tensor.
         hilo=True (f16 towers): the residual stream as a compensated f16 pair (GRIP_FWD_STREAM_HILO, include/grip_amd.h): the screen
-        of the pseudolabel pass -- a different (more accurate) function of the image than the plain f16 stream's, equally chunk-independent."""
+        of the pseudolabel pass -- a different (more accurate) function of the image than the plain f16 stream's, equally chunk-independent.
+        prefix: None, one prompt for every image ([P, d] / [1, P, d]), or one prompt per image aligned with `images`: [N, P, d] on any
+        device, N >= hi; rows lo .. hi are read chunk by chunk with their images."""
         if not self._finalized:
             self.finalize()
+        per_image = is_per_image_prefix(prefix)
         P = 0 if prefix is None else prefix.shape[-2]
-        if prefix is not None:
+        if per_image:
+            if prefix.shape[0] < hi or prefix.shape[2] != self.width:
+                raise native.GripError(f"per-image visual prompts of shape {tuple(prefix.shape)} do not cover images {lo} .. {hi} (width {self.width})")
+        elif prefix is not None:
             prefix = prefix.reshape(P, self.width).contiguous().float()
         if not hasattr(self, "_enc_streams"):
             self._enc_streams = [torch.cuda.Stream(device=self.device), torch.cuda.Stream(device=self.device)]
@@ -227,20 +247,28 @@ class Tower:
                     x = x.float()
                 if streams == 2:
                     x.record_stream(self._enc_streams[k])
+                pre = prefix
+                if per_image:       # this chunk's prompts, moved and cast on the chunk's stream like its images
+                    pre = prefix[s:e].to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
+                    if streams == 2:
+                        pre.record_stream(self._enc_streams[k])
                 o = out[s - lo: e - lo]
                 p, n = self._aligned(self._enc_ws[k])
-                native.check(self.lib.grip_vit_forward(self.handle, _ptr(x), int(x.dtype == torch.float16), _ptr(prefix), P, e - s, _ptr(o), p, n,
-                                                       native.FWD_STREAM_HILO if (hilo and self.precision == 0) else 0, None,
-                                                       c_void_p((self._enc_streams[k] if streams == 2 else main).cuda_stream)))
+                flags = (native.FWD_STREAM_HILO if (hilo and self.precision == 0) else 0) | (native.FWD_PER_IMAGE_PREFIX if per_image else 0)
+                native.check(self.lib.grip_vit_forward(self.handle, _ptr(x), int(x.dtype == torch.float16), _ptr(pre), P, e - s, _ptr(o), p, n,
+                                                       flags, None, c_void_p((self._enc_streams[k] if streams == 2 else main).cuda_stream)))
         for st in self._enc_streams:
             main.wait_stream(st)
         return out
 
     def vit_backward(self, grad_emb, prefix, ws, generation=0):
-        P = prefix.shape[-2]
-        prefix = prefix.reshape(P, self.width).contiguous().float()
+        """Prompt gradient of the train-mode forward on `ws`: [P, d] for a shared prompt (summed over the batch), [B, P, d] for per-image prompts."""
         grad_emb = grad_emb.contiguous().float()
-        g = torch.empty(P, self.width, dtype=torch.float32, device=self.device)
+        prefix, P, per_image = self.vit_prefix(prefix, grad_emb.shape[0])
+        if getattr(ws, "per_image", 0) != (grad_emb.shape[0] if per_image else 0):
+            raise native.GripError(f"vit_backward: the prompt of shape {tuple(prefix.shape)} is not the one the forward on this workspace read "
+                                   f"({'per image, batch ' + str(ws.per_image) if getattr(ws, 'per_image', 0) else 'shared'})")
+        g = torch.empty(prefix.shape, dtype=torch.float32, device=self.device)
         p, n = self._aligned(ws)
         native.check(self.lib.grip_vit_backward_prefix(self.handle, _ptr(grad_emb), _ptr(prefix), _ptr(g), p, n, generation, _stream()))
         return g
@@ -306,6 +334,11 @@ class Tower:
         return g
 
 
+def is_per_image_prefix(prefix):
+    """True for a visual prompt tensor that holds one prompt per image ([B, P, d] with B != 1); [P, d] and [1, P, d] are shared."""
+    return torch.is_tensor(prefix) and prefix.dim() == 3 and prefix.shape[0] != 1
+
+
 def vision_tower(d: ClipDims, device="cuda", max_prefix=64, exact=False):
     return Tower(0, d.vision_width, d.vision_layers, d.vision_heads, d.embed_dim, d.vision_seq, d.vision_patch_size,
                  d.image_resolution, 0, max_prefix, device, exact)
@@ -318,7 +351,10 @@ def text_tower(d: ClipDims, device="cuda", max_prefix=64, exact=False):
 
 # ------------------------------------------------------------------------------------------ autograd
 class VitPrefixFn(torch.autograd.Function):
-    """CustomVisionTransformer.forward with autograd to the visual prompt only (frozen backbone)."""
+    """CustomVisionTransformer.forward with autograd to the visual prompt only (frozen backbone).  The prompt follows the reference's
+    image_prefix.expand(B, -1, -1): [P, d] / [1, P, d] shared by the batch, or [B, P, d] one prompt per image; the gradient comes back in
+    the prompt's own shape and dtype ([B, P, d]: each image's own gradient, no sum over the batch).  The HIP-graph training steps
+    (steps.GraphedVptStep) capture shared prompts only: a per-image prompt runs this function eagerly."""
 
     @staticmethod
     def forward(ctx, tower, images, prefix, pos_emb=True):

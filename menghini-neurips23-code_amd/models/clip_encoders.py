@@ -69,7 +69,10 @@ class ImageEncoder(nn.Module):
 
 
 class CustomVisionTransformer(nn.Module):
-    """Reference :105-194: ViT with a visual prompt inserted between CLS and the patches."""
+    """Reference :105-194: ViT with a visual prompt inserted between CLS and the patches.  image_prefix follows the reference's
+    image_prefix.expand(B, -1, -1) (:148): [P, d] or [1, P, d] is one prompt shared by the batch, [B, P, d] one prompt per image
+    (instance-conditioned prompts, or several prompt sets in one batch); autograd returns the gradient in the prompt's own shape --
+    [B, P, d] per image.  Any other leading size raises, as expand does."""
 
     def __init__(self, vision_transformer):
         super().__init__()
@@ -93,7 +96,7 @@ class CustomVisionTransformer(nn.Module):
 
 
 class CustomImageEncoder(nn.Module):
-    """Reference :198-208."""
+    """Reference :198-208.  prefix: [P, d] / [1, P, d] shared, or [B, P, d] one prompt per image (CustomVisionTransformer)."""
 
     def __init__(self, visual):
         super().__init__()

@@ -11,8 +11,9 @@ from ctypes import POINTER, c_char, c_float, c_int, c_int32, c_int64, c_size_t, 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GRIP_LIB") or os.path.join(_HERE, "libgrip_amd.so")      # GRIP_LIB: another build of the same ABI (developer A/B)
 HOST_LIB_PATH = os.environ.get("GRIP_HOST_LIB")       # developer: a sanitizer build of the host-only sources (`make -C csrc sanitize`) whose grip_leaderboard_* / grip_bpe_* replace the library's
-ABI_VERSION = 8
+ABI_VERSION = 9
 FWD_TRAIN, FWD_SHARED_PREFIX, FWD_NO_POS_EMB, FWD_STREAM_HILO = 1, 2, 4, 8      # grip_vit_forward / grip_text_forward flags
+FWD_PER_IMAGE_PREFIX = 32      # grip_vit_forward (ABI 9): prefix [batch, n_prefix, width], one prompt per image
 
 
 class GripError(RuntimeError):

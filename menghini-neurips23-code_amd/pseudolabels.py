@@ -120,10 +120,14 @@ def encode_pool(visual_tower, images, chunk=880, prefix=None, out=None, screen=F
     """Encode an ordered pool.  `images` is a tensor [N,3,R,R] (any device) or a callable
     (lo, hi) -> tensor for that slice.  With torch.distributed initialised the pool is sharded
     contiguously and the embeddings are all-gathered; returns [N, E] f32 on the device.
-    screen: False, or the stream form ("hilo" / "f16") of a screen-and-refine pass's screen; True = screen_stream() without a pool history."""
+    screen: False, or the stream form ("hilo" / "f16") of a screen-and-refine pass's screen; True = screen_stream() without a pool history.
+    prefix: None, one visual prompt for the whole pool ([P, d] / [1, P, d]), or one per image ([N, P, d], aligned with `images`: each rank
+    reads the prompts of its own shard)."""
     if screen is True:
         screen = screen_stream()
     n = images.shape[0] if torch.is_tensor(images) else images.n
+    if engine.is_per_image_prefix(prefix) and prefix.shape[0] != n:
+        raise ValueError(f"per-image visual prompts [{prefix.shape[0]}, P, d] for a pool of {n} images")
     lo, hi, per = gdist.shard_range(n)
     dev = visual_tower.device
     local = torch.empty(max(hi - lo, 0), visual_tower.embed_dim, dtype=torch.float32, device=dev)
@@ -550,6 +554,14 @@ def take_images(images, idx):
     return images.take(idx)
 
 
+def take_prefix(prefix, idx):
+    """The visual prompts of rows `idx` (ascending int64 array) of a pool, to go with take_images(images, idx): rows of a per-image prompt
+    [N, P, d]; a shared prompt (None, [P, d], [1, P, d]) is every row's and comes back as it is."""
+    if not engine.is_per_image_prefix(prefix):
+        return prefix
+    return prefix[torch.as_tensor(idx, device=prefix.device)]
+
+
 def balanced_chunk(n_rows, chunk):
     """Rows per launch when `n_rows` rows go through a tower at most `chunk` at a time: the smallest size that keeps the number of launches
     (1 024 audit rows at 880 -> 2 x 512, not 880 + 144: the tail launch left the 256 x 256 GEMM tiles of the refinement towers a chip's worth of
@@ -561,6 +573,7 @@ def balanced_chunk(n_rows, chunk):
 def tier_rows(tower, fetch, txt, scale, n, lo, hi, chunk, prefix=None, argmax_on="probs", on_rows=None, timer=None):
     """A refinement tier as refine_scan's callback: rows(idx) -> (probs [len(idx), C], arg-max) of the global rows `idx` (ascending) re-encoded by `tower`.
     Each rank encodes the rows of its own shard [lo, hi) -- `fetch(global_rows)` returns their images -- and one padded all-gather assembles the rest.
+    prefix: None, a shared visual prompt, or per-image prompts [n, P, d] aligned with the pool (the rows' own prompts go with them: take_prefix).
     rows.submit(idx) only ENQUEUES the work, on the tier's own HIP stream, and returns the function that waits for it: two tiers submitted back to back
     (refine_scan does that wherever their row sets are independent) share the GPU instead of taking turns at small-batch efficiency."""
     dev = tower.device
@@ -574,7 +587,8 @@ def tier_rows(tower, fetch, txt, scale, n, lo, hi, chunk, prefix=None, argmax_on
         with torch.cuda.stream(side):
             local = torch.empty(len(mine), tower.embed_dim, dtype=torch.float32, device=dev)
             if len(mine):
-                tower.encode_chunks(lambda a, b: fetch(mine[a:b]), local, 0, len(mine), balanced_chunk(len(mine), chunk), prefix, streams=tier_streams())
+                tower.encode_chunks(lambda a, b: fetch(mine[a:b]), local, 0, len(mine), balanced_chunk(len(mine), chunk), take_prefix(prefix, mine),
+                                    streams=tier_streams())
             if on_rows is not None:
                 on_rows(len(mine))
             got = gdist.allgather_selected(local, idx, n, tag="refined_rows")
@@ -608,7 +622,8 @@ def identical_lists(visual16, visual32, images, txt_exact, scale, paths, class_l
     f32 tower `visual32` what that tier cannot decide either (each rank re-encodes the marked rows of its own shard; one small
     all-gather per round and tier).  The lists are the exact mode's lists provided every row obeys the measured bound of the tier it
     was left at; the bound is calibrated on this pool, audited on a hold-out sample after certification and reported in
-    LAST_REFINE_STATS (asserted equal to the exact mode at N = 50 000 in tests/test_gpu_identical.py)."""
+    LAST_REFINE_STATS (asserted equal to the exact mode at N = 50 000 in tests/test_gpu_identical.py).  prefix: None, one visual prompt for
+    the pool, or one per image ([N, P, d]): every tier encodes a row with its own prompt."""
     global LAST_REFINE_STATS
     n = len(paths)
     if n == 0:

@@ -306,7 +306,8 @@ def lookahead_image_features(clip_model, batches, group=8, overlap=None):
 
 
 class GraphedVptStep(GraphedStep):
-    """vpt_step (visual prompt: image tower forward + backward; text features fixed for the epoch) replayed from a HIP graph."""
+    """vpt_step (visual prompt: image tower forward + backward; text features fixed for the epoch) replayed from a HIP graph.  The graph
+    captures a shared prompt ([P, d] / [1, P, d]); a model whose prompt is per image ([B, P, d]) runs the eager step."""
 
     def __init__(self, model, text_features, logit_scale, optimizer):
         super().__init__(optimizer)
@@ -317,6 +318,12 @@ class GraphedVptStep(GraphedStep):
 
     def forward_logits(self):
         return CosineHeadFn.apply(self.model(self.x), self.text_features, self.scale)
+
+    def __call__(self, images, labels, row_weight):
+        if engine.is_per_image_prefix(self.model.prefix):
+            loss, self.logits = self.eager(images, labels, row_weight)
+            return loss
+        return super().__call__(images, labels, row_weight)
 
     def eager(self, images, labels, row_weight):
         return vpt_step(self.model, self.text_features, self.scale, images, labels, row_weight, self.optimizer, return_logits=True)
