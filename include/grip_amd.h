@@ -124,6 +124,16 @@ int grip_workspace_bytes(const grip_tower* t, int batch, int n_prefix, int seq_l
 int grip_vit_forward(grip_tower* t, const void* images, int images_f16, const float* prefix, int n_prefix,
                      int batch, float* out_emb, void* workspace, size_t workspace_bytes, int flags, uint64_t* generation, void* stream);
 
+/* Deep visual prompts (VPT-Deep; ABI 9 addition -- grip_vit_forward is this call with deep = NULL, n_deep = 0, and runs exactly as before):
+ *   deep       [n_deep, n_prefix, width] f32, shared by the batch.  Before block l (1 <= l <= n_deep) the rows 1 .. n_prefix of every image's
+ *              residual stream are replaced by deep[l - 1]: no LayerNorm, no positional embedding (the reference's deep_embs branch,
+ *              models/clip_encoders.py:166-184, with its vpt_proj / vpt_dropout as identity).  Block 0 reads the shallow prompt as above.
+ *   n_deep     0 .. layers - 1; n_deep > 0 needs n_prefix > 0 and deep != NULL, and is refused with GRIP_FWD_PER_IMAGE_PREFIX and on a text tower.
+ * Every tower precision and flag otherwise as grip_vit_forward.  A train-mode forward records n_deep: its backward is grip_vit_backward_deep
+ * (grip_vit_backward_prefix then fails with GRIP_ERR_STATE). */
+int grip_vit_forward_deep(grip_tower* t, const void* images, int images_f16, const float* prefix, int n_prefix, const float* deep, int n_deep,
+                          int batch, float* out_emb, void* workspace, size_t workspace_bytes, int flags, uint64_t* generation, void* stream);
+
 /* Input-gradient chain of the frozen ViT down to the prompt slice (autograd of the above w.r.t.
  * image_prefix only; no weight gradients exist).  Must follow a train-mode forward on the same
  * workspace, exactly once per forward; generation = the number that forward returned (0 = do not check).  grad_emb [batch, embed_dim] f32 -> grad_prefix [n_prefix, width] f32 (summed over batch).
@@ -131,6 +141,13 @@ int grip_vit_forward(grip_tower* t, const void* images, int images_f16, const fl
  * prompt gradient alone, no sum over the batch (autograd of image_prefix [B, P, d]); bit-reproducible (no atomics, one writer per element). */
 int grip_vit_backward_prefix(grip_tower* t, const float* grad_emb, const float* prefix, float* grad_prefix,
                              void* workspace, size_t workspace_bytes, uint64_t generation, void* stream);
+
+/* The same after grip_vit_forward_deep (ABI 9 addition): grad_prefix as grip_vit_backward_prefix, and grad_deep [n_deep, n_prefix, width] f32 -- grad_deep[l - 1]
+ * is the gradient of the stream rows 1 .. n_prefix entering block l, summed over the batch in a fixed order (no atomics: the same bits on every run).
+ * Those rows get no gradient below block l (they were overwritten), so the shallow prompt's gradient flows through block 0 alone.  After a forward
+ * without deep prompts grad_deep is not touched (may be NULL). */
+int grip_vit_backward_deep(grip_tower* t, const float* grad_emb, const float* prefix, float* grad_prefix, float* grad_deep,
+                           void* workspace, size_t workspace_bytes, uint64_t generation, void* stream);
 
 /* CustomTextEncoder.forward(class_embeddings, classes) / clip_model.encode_text(tokens)
  * (models/clip_encoders.py:43-90; :13-22 with n_prefix = 0).  Tokenisation stays on the host.

@@ -222,6 +222,9 @@ int launch_im2col(const void* images, int images_f16, void* out, int out_f32, in
 int launch_vit_assemble_ln(const float* patch_out, const float* cls, const float* pos, const float* prefix, int P,   /* x_lo (last argument, optional): the lo parts of a compensated stream */
                            const float* gamma, const float* beta, void* x, int f32, float* rowstat, int B, int G2, int d, hipStream_t s, half_t* x_lo = nullptr,
                            int per_image = 0);   /* per_image: prefix is [B, P, d] (one prompt per image), else [P, d] shared by the batch */
+// deep visual prompts: rows (b, 1 .. P) of the stream entering a block := deep [P, d] for every image; x_lo / stat_part / rowstat (each optional):
+// the compensated stream's lo parts and the row statistics of the values as stored (stat_part [d/64, M, 2] partial pairs, rowstat [M, 2] finalised)
+int launch_vit_deep_insert(const float* deep, void* x, int f32, half_t* x_lo, float* stat_part, float* rowstat, int B, int S, int P, int M, int d, hipStream_t s);
 // rowstat [M, 2] = (mean, rstd) of every row from the [M, parts, 2] partial sums the residual GEMM epilogues emit
 int launch_ln_stats_finalize(const float* stat_part, int parts, float* rowstat, int M, int d, hipStream_t s);
 // W' = f16(gamma o W) [N, K]; colsum[n] = sum_k W'[n][k]; bias_out[n] = bias[n] + sum_k beta[k] W[n][k]
@@ -280,6 +283,8 @@ int launch_ln_bwd_scatter_fill(const resid_t* x, const float* dy, const int32_t*
                                int n, int M, int d, hipStream_t s);
 int launch_vit_prefix_grad(const float* dx, const float* prefix, const float* gamma, const float* scale, float* grad, int B, int S, int P, int d, hipStream_t s);
 // per-image prompts (GRIP_FWD_PER_IMAGE_PREFIX): prefix / grad [B, P, d], no sum over the batch
+// deep visual prompts: grad[p] = inv_scale * sum_b dx[b*S + 1 + p] (no LayerNorm), then rows (b, 1 + p) of dx and dxh := 0
+int launch_vit_deep_grad(float* dx, half_t* dxh, const float* scale, float* grad, int B, int S, int P, int d, hipStream_t s);
 int launch_vit_prefix_grad_per_image(const float* dx, const float* prefix, const float* gamma, const float* scale, float* grad, int B, int S, int P, int d, hipStream_t s);
 int launch_text_prefix_grad(const float* dx, const float* scale, float* grad, int C, int T, int P, int prefix_classes, int d, hipStream_t s);
 int launch_grad_scale_cast(const float* g, half_t* g16, float* scale, int n, hipStream_t s);

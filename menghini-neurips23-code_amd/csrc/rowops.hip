@@ -149,6 +149,84 @@ int launch_vit_assemble_ln(const float* patch_out, const float* cls, const float
 }
 
 // ------------------------------------------------------------------------------------------------
+// Deep visual prompts (grip_vit_forward_deep): row (b, 1 + p) of the residual stream entering a block := deep[p], every image, no LayerNorm and no
+// positional embedding.  The kernel writes every form of stream the tower carries, as the assembly above does: the f16 stream (RT = resid_t) with,
+// when given, the lo part of a compensated stream (v - f16(v)) and the statistics the next LayerNorm-folded QKV GEMM reads, or the f32 stream of
+// the f32 / split-f16 towers (RT = float).  The statistics are those of the values as stored (hi, plus lo when compensated), in the residual
+// epilogue's convention (gemm.hip EPI_BIAS_RESID_STATS): per 64-column tile (sum, sum of squares), laid out [d/64][M] in stat_part (train-mode
+// forwards, whose consumer adds the pairs itself), or those pairs added in tile order into (mean, rstd) with ln_stats_finalize's arithmetic (rowstat).
+// One wave per (image, prompt token) row.
+template <int NV, typename RT>
+__global__ __launch_bounds__(256) void vit_deep_insert_kernel(const float* __restrict__ deep, RT* __restrict__ x, half_t* __restrict__ x_lo,
+                                                              float* __restrict__ stat_part, float* __restrict__ rowstat, int B, int S, int P, int M, int d) {
+#pragma clang fp contract(off)      // (the statistics round as ln_stats_finalize's do)
+    const int lane = threadIdx.x & 63;
+    const int idx = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (idx >= B * P) return;
+    const int b = idx / P, p = idx - b * P;
+    const size_t row = (size_t)b * S + 1 + p;
+    const int d4 = d >> 2;
+    const f32x4* src = (const f32x4*)(deep + (size_t)p * d);
+    f32x4 v[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+        if (lane + 64 * i < d4) {
+            v[i] = src[lane + 64 * i];
+            store4(x + row * d, lane + 64 * i, v[i]);
+            if constexpr (sizeof(RT) == 2) {
+                const f32x4 hi = {(float)(half_t)v[i][0], (float)(half_t)v[i][1], (float)(half_t)v[i][2], (float)(half_t)v[i][3]};
+                if (x_lo) {     // compensated stream: hi + lo as the assembly writes it
+                    const f32x4 lo = v[i] - hi;
+                    store4(x_lo + row * d, lane + 64 * i, lo);
+                    v[i] = hi + (f32x4){(float)(half_t)lo[0], (float)(half_t)lo[1], (float)(half_t)lo[2], (float)(half_t)lo[3]};
+                } else {
+                    v[i] = hi;
+                }
+            }
+        }
+    if (!stat_part && !rowstat) return;
+    float sm = 0.f, sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        float ts = 0.f, tq = 0.f;      // this lane's share of 64-column tile 4 i + lane / 16 (lanes outside the row add zero)
+        if (lane + 64 * i < d4) {
+            ts = (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+            tq = __builtin_fmaf(v[i][0], v[i][0], __builtin_fmaf(v[i][1], v[i][1], __builtin_fmaf(v[i][2], v[i][2], v[i][3] * v[i][3])));
+        }
+        ts = row16_sum(ts);
+        tq = row16_sum(tq);
+        if (stat_part && (lane & 15) == 0 && lane + 64 * i < d4)
+            ((float2*)stat_part)[(size_t)(4 * i + (lane >> 4)) * M + row] = make_float2(ts, tq);
+#pragma unroll
+        for (int g = 0; g < 4; ++g)      // the row's pairs in tile order
+            if (64 * i + 16 * g < d4) {
+                sm += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ts), 16 * g));
+                sq += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, tq), 16 * g));
+            }
+    }
+    if (rowstat && lane == 0) {
+        const float inv_d = 1.0f / (float)d;
+        const float mean = sm * inv_d;
+        const float var = fmaxf(sq * inv_d - mean * mean, 0.f);
+        ((float2*)rowstat)[row] = make_float2(mean, rsqrtf(var + LN_EPS));
+    }
+}
+
+int launch_vit_deep_insert(const float* deep, void* x, int f32, half_t* x_lo, float* stat_part, float* rowstat, int B, int S, int P, int M, int d, hipStream_t s) {
+    GRIP_REQUIRE(B > 0 && P > 0 && S >= 1 + P && M >= B * S, "vit_deep_insert: bad shape (B=%d P=%d S=%d M=%d)", B, P, S, M);
+    GRIP_REQUIRE(!(stat_part || rowstat) || (d % 64 == 0 && !f32), "vit_deep_insert: row statistics need an f16 stream of width %% 64 == 0 (width %d)", d);
+    const int rows = B * P;
+    if (f32) {
+        GRIP_REQUIRE(!x_lo && !stat_part && !rowstat, "vit_deep_insert: the f32 stream carries no lo part or statistics");
+        DISPATCH_NV(d, hipLaunchKernelGGL((vit_deep_insert_kernel<NV, float>), dim3((rows + 3) / 4), dim3(256), 0, s, deep, (float*)x, (half_t*)nullptr, stat_part, rowstat, B, S, P, M, d));
+    } else {
+        DISPATCH_NV(d, hipLaunchKernelGGL((vit_deep_insert_kernel<NV, resid_t>), dim3((rows + 3) / 4), dim3(256), 0, s, deep, (resid_t*)x, x_lo, stat_part, rowstat, B, S, P, M, d));
+    }
+    GRIP_CHECK_HIP(hipGetLastError());
+    return GRIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Text embedding (models/clip_encoders.py:63-74): x[c, t] = (1 <= t <= P ? prefix[c or 0, t-1] : tok_emb[ids[c, t]]) + pos[t];
 // pos == nullptr is the reference's enable_pos_emb=False branch (:70-74): no positional term.
 template <typename RT>

@@ -232,9 +232,12 @@ __global__ __launch_bounds__(256) void ln_bwd_scatter_fill_kernel(const resid_t*
 // Visual prompt slice through ln_pre: grad_prefix[s] = inv_scale * sum_b LNbwd(dx[b*S + 1 + s]; prefix[s]).
 // One workgroup of 8 waves per prompt token: wave w sums the images b = w (mod 8) in order, the eight partial rows meet in LDS and wave 0
 // adds them in wave order (deterministic).  (Until r03 one wave walked the whole batch: 16 dependent LayerNorm-backward rows = 32 us.)
-template <int NV>
+// LN = false, ZERO = true: a deep prompt's slice (grip_vit_backward_deep) -- the stream rows were overwritten, not normalised, so their gradient is
+// summed as it stands, and each wave then zeroes the rows it read in dx and dxh: nothing of them reaches the block below.  Same order of adds.
+template <int NV, bool LN = true, bool ZERO = false>
 __global__ __launch_bounds__(512) void vit_prefix_grad_kernel(const float* __restrict__ dx, const float* __restrict__ prefix, const float* __restrict__ gamma,
-                                                              const float* __restrict__ scale, float* __restrict__ grad, int B, int S, int P, int d) {
+                                                              const float* __restrict__ scale, float* __restrict__ grad, int B, int S, int P, int d,
+                                                              half_t* __restrict__ dxh = nullptr) {
     __shared__ f32x4 part[7][64 * NV];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = blockIdx.x;
@@ -244,10 +247,25 @@ __global__ __launch_bounds__(512) void vit_prefix_grad_kernel(const float* __res
     for (int i = 0; i < NV; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int b = wave; b < B; b += 8) {
         f32x4 g[NV];
-        ln_bwd_row<NV>(prefix + (size_t)s * d, (const f32x4*)(dx + ((size_t)b * S + 1 + s) * d), (const f32x4*)gamma, lane, d4, d, g);
+        const size_t row = (size_t)b * S + 1 + s;
+        if constexpr (LN) {
+            ln_bwd_row<NV>(prefix + (size_t)s * d, (const f32x4*)(dx + row * d), (const f32x4*)gamma, lane, d4, d, g);
+        } else {
+#pragma unroll
+            for (int i = 0; i < NV; ++i)
+                if (lane + 64 * i < d4) g[i] = ((const f32x4*)(dx + row * d))[lane + 64 * i];
+        }
 #pragma unroll
         for (int i = 0; i < NV; ++i)
             if (lane + 64 * i < d4) acc[i] += g[i];
+        if constexpr (ZERO) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i)
+                if (lane + 64 * i < d4) {
+                    ((f32x4*)((float*)dx + row * d))[lane + 64 * i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                    ((half4*)(dxh + row * d))[lane + 64 * i] = (half4){(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
+                }
+        }
     }
     if (wave != 0) {
 #pragma unroll
@@ -429,6 +447,13 @@ int launch_ln_bwd_scatter_fill(const resid_t* x, const float* dy, const int32_t*
 }
 int launch_vit_prefix_grad(const float* dx, const float* prefix, const float* gamma, const float* scale, float* grad, int B, int S, int P, int d, hipStream_t s) {
     DISPATCH_NV_B(d, hipLaunchKernelGGL(vit_prefix_grad_kernel<NV>, dim3(P), dim3(512), 0, s, dx, prefix, gamma, scale, grad, B, S, P, d));
+    GRIP_CHECK_HIP(hipGetLastError());
+    return GRIP_OK;
+}
+int launch_vit_deep_grad(float* dx, half_t* dxh, const float* scale, float* grad, int B, int S, int P, int d, hipStream_t s) {
+    GRIP_REQUIRE(B > 0 && P > 0 && S >= 1 + P && dx && dxh, "vit_deep_grad: bad arguments (B=%d P=%d S=%d)", B, P, S);
+    DISPATCH_NV_B(d, hipLaunchKernelGGL((vit_prefix_grad_kernel<NV, false, true>), dim3(P), dim3(512), 0, s, dx, (const float*)nullptr, (const float*)nullptr,
+                                        scale, grad, B, S, P, d, dxh));
     GRIP_CHECK_HIP(hipGetLastError());
     return GRIP_OK;
 }

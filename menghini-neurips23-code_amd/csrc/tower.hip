@@ -199,6 +199,8 @@ struct Workspace {  // carve of the caller's buffer for one (batch, n_prefix, tr
     half_t* row_x_lo = nullptr;   // ... and of the last block's compact read rows
     half_t* x_lo = nullptr;    // inference, f16 towers: the lo parts of the stream when the forward runs with GRIP_FWD_STREAM_HILO (GemmArgs::resid_lo)
     int hilo = 0;              // ... and whether this forward does
+    const float* deep = nullptr;   // deep visual prompts [n_deep, P, d] f32 (grip_vit_forward_deep): rows 1 .. P of block l's input := deep[l - 1], 1 <= l <= n_deep
+    int n_deep = 0;
     // train-mode saves, one per layer (x_in has layers+1 entries)
     std::vector<resid_t*> x_in, x_mid;
     std::vector<half_t*> qkv_l, att_l, hpre_l;
@@ -248,6 +250,7 @@ struct grip_tower {
         const int32_t* eot = nullptr;
         int prefix_classes = 0;
         bool per_image = false;    // vision: the forward ran with GRIP_FWD_PER_IMAGE_PREFIX (prefix and its gradient are [batch, n_prefix, width])
+        int n_deep = 0;            // vision: deep visual prompts of the forward (grip_vit_forward_deep): its backward is grip_vit_backward_deep
         uint64_t generation = 0;
         bool consumed = false;     // its backward has run (the backward works in place on the saved activations: one per forward)
     };
@@ -485,6 +488,9 @@ static int run_blocks(grip_tower* t, Workspace& w, resid_t* x0, int causal, cons
     for (int l = 0; l < t->D.layers; ++l) {
         const LayerW& lw = t->L.layer[(size_t)l];
         const bool last = l + 1 == t->D.layers;
+        if (l >= 1 && l <= w.n_deep)      // deep prompts: the block's input rows 1 .. P := deep[l - 1] before anything reads x (train: x_in[l], what the backward differentiates)
+            RUN(launch_vit_deep_insert(w.deep + (size_t)(l - 1) * w.P * d, x, f, hilo ? w.x_lo : nullptr, parts_in ? w.stat_part : nullptr,
+                                       (fold && !parts_in) ? w.rowstat : nullptr, w.batch, w.S, w.P, (int)w.M, d, s));
         if (last && rows_only) {
             // K and V of every row (columns d .. 3d of the packed projection); Q only for the rows that are read
             GemmArgs a{};
@@ -640,7 +646,7 @@ static int check_ws(grip_tower* t, int batch, int P, int train, void* ws, size_t
 // Book-keeping of a finished forward: a train-mode one registers its state under the workspace (replacing whatever
 // forward used that workspace before) and hands out a fresh generation number; an inference one invalidates it.
 static void note_forward(grip_tower* t, void* workspace, int train, const Workspace& w, const int32_t* eot, int prefix_classes, uint64_t* generation,
-                         bool per_image = false) {
+                         bool per_image = false, int n_deep = 0) {
     if (train) {
         // Consumed entries only serve a clearer error message ("already back-propagated"); workspaces that were freed since (pools dropped with a
         // key change, graph pins released per GRIP iteration) would otherwise stay in the map for good, and a recycled address could hit a stale one.
@@ -648,7 +654,7 @@ static void note_forward(grip_tower* t, void* workspace, int train, const Worksp
             for (auto it = t->pending.begin(); it != t->pending.end();)
                 it = (it->second.consumed && it->first != workspace) ? t->pending.erase(it) : std::next(it);
         grip_tower::TrainState& st = t->pending[workspace];
-        st.w = w; st.eot = eot; st.prefix_classes = prefix_classes; st.per_image = per_image; st.generation = ++t->generation; st.consumed = false;
+        st.w = w; st.eot = eot; st.prefix_classes = prefix_classes; st.per_image = per_image; st.n_deep = n_deep; st.generation = ++t->generation; st.consumed = false;
         if (generation) *generation = st.generation;
     } else {
         t->pending.erase(workspace);
@@ -656,10 +662,15 @@ static void note_forward(grip_tower* t, void* workspace, int train, const Worksp
     }
 }
 
-extern "C" int grip_vit_forward(grip_tower* t, const void* images, int images_f16, const float* prefix, int n_prefix,
-                                int batch, float* out_emb, void* workspace, size_t workspace_bytes, int flags, uint64_t* generation, void* stream) {
+extern "C" int grip_vit_forward_deep(grip_tower* t, const void* images, int images_f16, const float* prefix, int n_prefix, const float* deep, int n_deep,
+                                     int batch, float* out_emb, void* workspace, size_t workspace_bytes, int flags, uint64_t* generation, void* stream) {
     try {
-        GRIP_REQUIRE(t && t->D.kind == 0, "vit_forward: not a vision tower");
+        GRIP_REQUIRE(t && t->D.kind == 0, "vit_forward: not a vision tower%s", n_deep ? " (deep prompts are a vision-tower feature)" : "");
+        GRIP_REQUIRE(n_deep >= 0 && n_deep <= t->D.layers - 1, "vit_forward_deep: n_deep = %d out of range: deep prompts replace the prompt rows entering blocks 1 .. n_deep, "
+                     "0 <= n_deep <= layers - 1 = %d", n_deep, t->D.layers - 1);
+        GRIP_REQUIRE(n_deep == 0 || n_prefix > 0, "vit_forward_deep: deep prompts replace the rows of the shallow prompt: n_prefix must be positive (n_deep = %d)", n_deep);
+        GRIP_REQUIRE(n_deep == 0 || deep, "vit_forward_deep: null deep prompt pointer (n_deep = %d)", n_deep);
+        GRIP_REQUIRE(n_deep == 0 || !(flags & GRIP_FWD_PER_IMAGE_PREFIX), "vit_forward_deep: deep prompts are shared by the batch: not valid with GRIP_FWD_PER_IMAGE_PREFIX");
         GRIP_REQUIRE((flags & ~(GRIP_FWD_TRAIN | GRIP_FWD_NO_POS_EMB | GRIP_FWD_STREAM_HILO | GRIP_FWD_PER_IMAGE_PREFIX)) == 0, "vit_forward: unknown flag bits 0x%x", flags);
         const int train = flags & GRIP_FWD_TRAIN;
         const int per_image = (flags & GRIP_FWD_PER_IMAGE_PREFIX) ? 1 : 0;      // prefix [batch, n_prefix, width]: rows (b, 1 .. P) read image b's prompt
@@ -667,6 +678,8 @@ extern "C" int grip_vit_forward(grip_tower* t, const void* images, int images_f1
         GRIP_REQUIRE(images && out_emb && (n_prefix == 0 || prefix), "vit_forward: null pointer");
         Workspace w;
         RUN(check_ws(t, batch, n_prefix, train, workspace, workspace_bytes, w));
+        w.deep = n_deep ? deep : nullptr;
+        w.n_deep = n_deep;
         hipStream_t s = (hipStream_t)stream;
         const grip_dims& D = t->D;
         const int d = D.width, G2 = D.seq0 - 1, f = t->f32;
@@ -686,9 +699,14 @@ extern "C" int grip_vit_forward(grip_tower* t, const void* images, int images_f1
         a = GemmArgs{};
         a.f32 = f; a.A = w.cls16; a.W = t->wop(t->L.projT); a.M = batch; a.N = D.embed_dim; a.K = d; a.out = out_emb; a.ldc = D.embed_dim;
         RUN(launch_gemm(EPI_F32, a, s));
-        note_forward(t, workspace, train, w, nullptr, 0, generation, per_image != 0);
+        note_forward(t, workspace, train, w, nullptr, 0, generation, per_image != 0, n_deep);
         return GRIP_OK;
     } catch (...) { grip_set_error("vit_forward: exception"); return GRIP_ERR_ARG; }
+}
+
+extern "C" int grip_vit_forward(grip_tower* t, const void* images, int images_f16, const float* prefix, int n_prefix,
+                                int batch, float* out_emb, void* workspace, size_t workspace_bytes, int flags, uint64_t* generation, void* stream) {
+    return grip_vit_forward_deep(t, images, images_f16, prefix, n_prefix, nullptr, 0, batch, out_emb, workspace, workspace_bytes, flags, generation, stream);
 }
 
 extern "C" int grip_text_forward(grip_tower* t, const int32_t* token_ids, const int32_t* eot_index, const float* prefix,
@@ -821,13 +839,17 @@ extern "C" int grip_debug_layernorm(const float* x, const float* gamma, const fl
 // ---------------------------------------------------------------------------------------------- backward
 // Input-gradient chain of one tower down to its prompt slice.  Enters with dx / dxh holding the
 // (loss-scaled) gradient w.r.t. the final residual stream, leaves with dx = gradient w.r.t. x0.
-static int run_blocks_backward(grip_tower* t, Workspace& w, int causal, const int32_t* read_rows, hipStream_t s) {
+// grad_deep (deep visual prompts, w.n_deep > 0): [n_deep, P, d]; before block l's backward, dx / dxh hold the gradient of x_in[l + 1], whose rows
+// 1 .. P the forward overwrote with deep[l] when l + 1 <= n_deep: their batch sum is grad_deep[l], and they are zeroed (nothing flows below).
+static int run_blocks_backward(grip_tower* t, Workspace& w, int causal, const int32_t* read_rows, hipStream_t s, float* grad_deep = nullptr) {
     const int d = t->D.width, H = t->D.heads;
     const half_t* W = t->w16;
     const float* F = t->w32;
     const int64_t part = (int64_t)w.Mp * d;       // floats between split-K partial buffers in w.dln
     for (int l = t->D.layers - 1; l >= 0; --l) {
         const LayerW& lw = t->L.layer[(size_t)l];
+        if (grad_deep && l + 1 <= w.n_deep)
+            RUN(launch_vit_deep_grad(w.dx, w.dxh, w.scale, grad_deep + (size_t)l * w.P * d, w.batch, w.S, w.P, d, s));
         if (l + 1 == t->D.layers && w.rows_last) {
             // the last block ran for the read rows only (run_blocks): enters with drow / drow_h = the gradient of those stream rows
             const int64_t Bp = round_up64(w.batch, 256);
@@ -927,6 +949,11 @@ extern "C" int grip_vit_backward_prefix(grip_tower* t, const float* grad_emb, co
                                         void* workspace, size_t workspace_bytes, uint64_t generation, void* stream) {
     try {
         GRIP_REQUIRE(t && t->D.kind == 0 && grad_emb && prefix && grad_prefix, "vit_backward_prefix: bad arguments");
+        auto it = t->pending.find(workspace);
+        if (it != t->pending.end() && it->second.n_deep > 0 && !it->second.consumed) {
+            grip_set_error("vit_backward_prefix: the forward on this workspace ran with %d deep prompts: its backward is grip_vit_backward_deep", it->second.n_deep);
+            return GRIP_ERR_STATE;
+        }
         grip_tower::TrainState st;
         RUN(check_bwd(t, workspace, workspace_bytes, generation, st));
         Workspace& w = st.w;
@@ -940,6 +967,28 @@ extern "C" int grip_vit_backward_prefix(grip_tower* t, const float* grad_emb, co
             RUN(launch_vit_prefix_grad(w.dx, prefix, t->w32 + t->L.lnpre_g, w.scale, grad_prefix, w.batch, w.S, w.P, t->D.width, s));
         return GRIP_OK;
     } catch (...) { grip_set_error("vit_backward_prefix: exception"); return GRIP_ERR_ARG; }
+}
+
+extern "C" int grip_vit_backward_deep(grip_tower* t, const float* grad_emb, const float* prefix, float* grad_prefix, float* grad_deep,
+                                      void* workspace, size_t workspace_bytes, uint64_t generation, void* stream) {
+    try {
+        GRIP_REQUIRE(t && t->D.kind == 0 && grad_emb && prefix && grad_prefix, "vit_backward_deep: bad arguments");
+        auto it = t->pending.find(workspace);
+        GRIP_REQUIRE(it == t->pending.end() || it->second.n_deep == 0 || grad_deep, "vit_backward_deep: null grad_deep (the forward ran with %d deep prompts)",
+                     it == t->pending.end() ? 0 : it->second.n_deep);
+        grip_tower::TrainState st;
+        RUN(check_bwd(t, workspace, workspace_bytes, generation, st));
+        Workspace& w = st.w;
+        GRIP_REQUIRE(w.P > 0, "vit_backward_deep: forward had no prompt tokens");
+        hipStream_t s = (hipStream_t)stream;
+        RUN(backward_head_of_tower(t, w, grad_emb, nullptr, s));
+        RUN(run_blocks_backward(t, w, 0, nullptr, s, st.n_deep ? grad_deep : nullptr));
+        if (st.per_image)
+            RUN(launch_vit_prefix_grad_per_image(w.dx, prefix, t->w32 + t->L.lnpre_g, w.scale, grad_prefix, w.batch, w.S, w.P, t->D.width, s));
+        else
+            RUN(launch_vit_prefix_grad(w.dx, prefix, t->w32 + t->L.lnpre_g, w.scale, grad_prefix, w.batch, w.S, w.P, t->D.width, s));
+        return GRIP_OK;
+    } catch (...) { grip_set_error("vit_backward_deep: exception"); return GRIP_ERR_ARG; }
 }
 
 extern "C" int grip_text_backward_prefix(grip_tower* t, const float* grad_emb, float* grad_prefix,

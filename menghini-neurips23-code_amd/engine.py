@@ -183,8 +183,17 @@ class Tower:
             return prefix.contiguous().float(), P, True
         return prefix.reshape(P, self.width).contiguous().float(), P, False
 
-    def vit_forward(self, images, prefix=None, train=False, pos_emb=True):
-        """CustomVisionTransformer.forward: images [B, 3, R, R]; prefix None, [P, d] / [1, P, d] (shared) or [B, P, d] (one prompt per image)."""
+    def vit_deep(self, deep, P):
+        """Deep visual prompts as the native call takes them: (deep f32 contiguous [D, P, d] or None, D).  deep[l - 1] replaces the prompt
+        rows of the stream entering block l, 1 <= l <= D <= layers - 1 (grip_vit_forward_deep, include/grip_amd.h)."""
+        if deep is None:
+            return None, 0
+        check_deep_prompts(deep, P, self.width, self.dims.layers)
+        return deep.contiguous().float(), deep.shape[0]
+
+    def vit_forward(self, images, prefix=None, train=False, pos_emb=True, deep=None):
+        """CustomVisionTransformer.forward: images [B, 3, R, R]; prefix None, [P, d] / [1, P, d] (shared) or [B, P, d] (one prompt per image);
+        deep None or [D, P, d] deep prompts (shared prompt only)."""
         if not self._finalized:
             self.finalize()
         assert self.kind == 0
@@ -193,19 +202,25 @@ class Tower:
             images = images.float()
         B = images.shape[0]
         prefix, P, per_image = self.vit_prefix(prefix, B)
+        deep, D = self.vit_deep(deep, P)
         out = torch.empty(B, self.embed_dim, dtype=torch.float32, device=self.device)
         ws = self.workspace(B, P, train)
         p, n = self._aligned(ws)
         gen = c_uint64(0)
         flags = (native.FWD_TRAIN if train else 0) | (0 if pos_emb else native.FWD_NO_POS_EMB) | (native.FWD_PER_IMAGE_PREFIX if per_image else 0)
-        native.check(self.lib.grip_vit_forward(self.handle, _ptr(images), int(images.dtype == torch.float16), _ptr(prefix), P, B,
-                                               _ptr(out), p, n, flags, byref(gen), _stream()))
+        if D:
+            native.check(self.lib.grip_vit_forward_deep(self.handle, _ptr(images), int(images.dtype == torch.float16), _ptr(prefix), P, _ptr(deep), D, B,
+                                                        _ptr(out), p, n, flags, byref(gen), _stream()))
+        else:
+            native.check(self.lib.grip_vit_forward(self.handle, _ptr(images), int(images.dtype == torch.float16), _ptr(prefix), P, B,
+                                                   _ptr(out), p, n, flags, byref(gen), _stream()))
         ws.generation = gen.value
         ws.per_image = B if per_image else 0      # the backward's grad_prefix is [B, P, d] then (vit_backward checks it is given that shape)
+        ws.n_deep = D                             # ... and grad_deep [D, P, d]
         return out, ws
 
     @torch.no_grad()
-    def encode_chunks(self, images, out, lo, hi, chunk, prefix=None, streams=2, hilo=False):
+    def encode_chunks(self, images, out, lo, hi, chunk, prefix=None, streams=2, hilo=False, deep=None):
         """Inference encode of images[lo:hi] into out[0:hi-lo] in chunks, alternating between two HIP streams (each
         with its own workspace): the HBM-bound kernels of one chunk (LayerNorm, attention, patch gather) run next to
         the power-bound GEMMs of the other.  Rows are independent of the chunking, so the result is bit-identical to
@@ -214,7 +229,8 @@ class Tower:
         hilo=True (f16 towers): the residual stream as a compensated f16 pair (GRIP_FWD_STREAM_HILO, include/grip_amd.h): the screen
         of the pseudolabel pass -- a different (more accurate) function of the image than the plain f16 stream's, equally chunk-independent.
         prefix: None, one prompt for every image ([P, d] / [1, P, d]), or one prompt per image aligned with `images`: [N, P, d] on any
-        device, N >= hi; rows lo .. hi are read chunk by chunk with their images."""
+        device, N >= hi; rows lo .. hi are read chunk by chunk with their images.
+        deep: None or [D, P, d] deep prompts of a shared prompt (every image alike, so still chunk-independent)."""
         if not self._finalized:
             self.finalize()
         per_image = is_per_image_prefix(prefix)
@@ -224,6 +240,11 @@ class Tower:
                 raise native.GripError(f"per-image visual prompts of shape {tuple(prefix.shape)} do not cover images {lo} .. {hi} (width {self.width})")
         elif prefix is not None:
             prefix = prefix.reshape(P, self.width).contiguous().float()
+        if deep is not None:
+            if per_image:
+                raise native.GripError("deep visual prompts need one prompt shared by every image, not per-image prompts")
+            deep = deep.to(self.device)
+        deep, D = self.vit_deep(deep, P)
         if not hasattr(self, "_enc_streams"):
             self._enc_streams = [torch.cuda.Stream(device=self.device), torch.cuda.Stream(device=self.device)]
             self._enc_ws = {}
@@ -255,14 +276,20 @@ class Tower:
                 o = out[s - lo: e - lo]
                 p, n = self._aligned(self._enc_ws[k])
                 flags = (native.FWD_STREAM_HILO if (hilo and self.precision == 0) else 0) | (native.FWD_PER_IMAGE_PREFIX if per_image else 0)
-                native.check(self.lib.grip_vit_forward(self.handle, _ptr(x), int(x.dtype == torch.float16), _ptr(pre), P, e - s, _ptr(o), p, n,
-                                                       flags, None, c_void_p((self._enc_streams[k] if streams == 2 else main).cuda_stream)))
+                st = c_void_p((self._enc_streams[k] if streams == 2 else main).cuda_stream)
+                if D:
+                    native.check(self.lib.grip_vit_forward_deep(self.handle, _ptr(x), int(x.dtype == torch.float16), _ptr(pre), P, _ptr(deep), D, e - s, _ptr(o),
+                                                                p, n, flags, None, st))
+                else:
+                    native.check(self.lib.grip_vit_forward(self.handle, _ptr(x), int(x.dtype == torch.float16), _ptr(pre), P, e - s, _ptr(o), p, n,
+                                                           flags, None, st))
         for st in self._enc_streams:
             main.wait_stream(st)
         return out
 
     def vit_backward(self, grad_emb, prefix, ws, generation=0):
-        """Prompt gradient of the train-mode forward on `ws`: [P, d] for a shared prompt (summed over the batch), [B, P, d] for per-image prompts."""
+        """Prompt gradient of the train-mode forward on `ws`: [P, d] for a shared prompt (summed over the batch), [B, P, d] for per-image prompts.
+        After a forward with deep prompts: (prompt gradient, deep-prompt gradient [D, P, d] summed over the batch)."""
         grad_emb = grad_emb.contiguous().float()
         prefix, P, per_image = self.vit_prefix(prefix, grad_emb.shape[0])
         if getattr(ws, "per_image", 0) != (grad_emb.shape[0] if per_image else 0):
@@ -270,6 +297,11 @@ class Tower:
                                    f"({'per image, batch ' + str(ws.per_image) if getattr(ws, 'per_image', 0) else 'shared'})")
         g = torch.empty(prefix.shape, dtype=torch.float32, device=self.device)
         p, n = self._aligned(ws)
+        D = getattr(ws, "n_deep", 0)
+        if D:
+            gd = torch.empty(D, P, self.width, dtype=torch.float32, device=self.device)
+            native.check(self.lib.grip_vit_backward_deep(self.handle, _ptr(grad_emb), _ptr(prefix), _ptr(g), _ptr(gd), p, n, generation, _stream()))
+            return g, gd
         native.check(self.lib.grip_vit_backward_prefix(self.handle, _ptr(grad_emb), _ptr(prefix), _ptr(g), p, n, generation, _stream()))
         return g
 
@@ -334,6 +366,14 @@ class Tower:
         return g
 
 
+def check_deep_prompts(deep, P, width, layers):
+    """Deep visual prompts must be [D, P, width] with 1 <= D <= layers - 1: the shallow prompt's token count P (they replace its rows) and one
+    prompt per block after the first.  Raises GripError otherwise."""
+    if deep.dim() != 3 or deep.shape[1] != P or deep.shape[2] != width or not 1 <= deep.shape[0] <= layers - 1:
+        raise native.GripError(f"deep visual prompts of shape {tuple(deep.shape)}: expected [D, {P}, {width}] with 1 <= D <= {layers - 1} "
+                               f"(the shallow prompt's P = {P} and width; one prompt per block after the first)")
+
+
 def is_per_image_prefix(prefix):
     """True for a visual prompt tensor that holds one prompt per image ([B, P, d] with B != 1); [P, d] and [1, P, d] are shared."""
     return torch.is_tensor(prefix) and prefix.dim() == 3 and prefix.shape[0] != 1
@@ -357,16 +397,17 @@ class VitPrefixFn(torch.autograd.Function):
     (steps.GraphedVptStep) capture shared prompts only: a per-image prompt runs this function eagerly."""
 
     @staticmethod
-    def forward(ctx, tower, images, prefix, pos_emb=True):
-        need = ctx.needs_input_grad[2]   # grad mode is off inside Function.forward
+    def forward(ctx, tower, images, prefix, pos_emb=True, deep=None):
+        need = ctx.needs_input_grad[2] or (deep is not None and ctx.needs_input_grad[4])   # grad mode is off inside Function.forward
         if need and tower.exact:
             raise native.GripError("exact (f32) towers are inference-only: prompt gradients need a default-precision tower")
-        out, ws = tower.vit_forward(images, prefix.detach(), train=need, pos_emb=pos_emb)
+        out, ws = tower.vit_forward(images, prefix.detach(), train=need, pos_emb=pos_emb, deep=None if deep is None else deep.detach())
         ctx.tower, ctx.ws, ctx.generation = tower, ws, ws.generation
         if need:
             tower.hold(ws, ctx)
         ctx.save_for_backward(prefix.detach())
         ctx.pshape, ctx.pdtype = prefix.shape, prefix.dtype
+        ctx.dshape, ctx.ddtype = (None, None) if deep is None else (deep.shape, deep.dtype)
         return out
 
     @staticmethod
@@ -374,7 +415,10 @@ class VitPrefixFn(torch.autograd.Function):
         (prefix,) = ctx.saved_tensors
         g = ctx.tower.vit_backward(grad_out, prefix, ctx.ws, ctx.generation)
         ctx.tower.release(ctx.ws)
-        return None, None, g.reshape(ctx.pshape).to(ctx.pdtype), None
+        if ctx.dshape is None:
+            return None, None, g.reshape(ctx.pshape).to(ctx.pdtype), None
+        g, gd = g
+        return None, None, g.reshape(ctx.pshape).to(ctx.pdtype), None, gd.reshape(ctx.dshape).to(ctx.ddtype)
 
 
 class TextPrefixFn(torch.autograd.Function):
@@ -402,14 +446,19 @@ class TextPrefixFn(torch.autograd.Function):
         return None, None, g.to(ctx.pdtype), None
 
 
-def vit_prefix_forward(tower, images, prefix, pos_emb=True):
+def vit_prefix_forward(tower, images, prefix, pos_emb=True, deep=None):
     """CustomVisionTransformer.forward on the native tower.  The train-mode forward (activations saved for the prompt
     gradient) runs only when a gradient can actually be asked for: grad mode on AND the prompt requires grad.  Under
     torch.no_grad() -- validation, test predictions, the pseudolabel passes -- it is the plain inference forward, the same
-    arithmetic as the pool encode (autograd's needs_input_grad alone does not see the surrounding no_grad)."""
-    if torch.is_grad_enabled() and prefix.requires_grad:
-        return VitPrefixFn.apply(tower, images, prefix, pos_emb)
-    return tower.vit_forward(images, prefix.detach(), train=False, pos_emb=pos_emb)[0]
+    arithmetic as the pool encode (autograd's needs_input_grad alone does not see the surrounding no_grad).
+    deep: None or [D, P, d] deep prompts (VPT-Deep); differentiable as well, the gradient in deep's shape and dtype."""
+    if deep is None:
+        if torch.is_grad_enabled() and prefix.requires_grad:
+            return VitPrefixFn.apply(tower, images, prefix, pos_emb)
+        return tower.vit_forward(images, prefix.detach(), train=False, pos_emb=pos_emb)[0]
+    if torch.is_grad_enabled() and (prefix.requires_grad or deep.requires_grad):
+        return VitPrefixFn.apply(tower, images, prefix, pos_emb, deep)
+    return tower.vit_forward(images, prefix.detach(), train=False, pos_emb=pos_emb, deep=deep.detach())[0]
 
 
 def text_prefix_forward(tower, token_ids, prefix, pos_emb=True):

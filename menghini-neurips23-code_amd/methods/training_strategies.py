@@ -73,9 +73,16 @@ class TrainingStrategy:
             self.initial_prefix = init(1, int(c.PREFIX_SIZE), d.transformer_width)
         elif self.modality == "image":
             self.initial_prefix = init(int(c.PREFIX_SIZE), d.vision_width)
+            # VPT_DEEP: deep prompts for blocks 1 .. layers - 1, drawn after the shallow prompt (which stays bit-identical with and without them)
+            self.initial_deep_prefix = init(d.vision_layers - 1, int(c.PREFIX_SIZE), d.vision_width) if self.vpt_deep() else None
         else:
             self.coop_init = init(1, int(c.TEXT_PREFIX_SIZE), d.transformer_width)
             self.vpt_init = init(1, int(c.VISION_PREFIX_SIZE), d.vision_width)
+
+    def vpt_deep(self):
+        """Deep visual prompts (VPT-Deep) for the visual strategies: config VPT_DEEP, default False.  The multimodal strategies keep the reference's
+        behaviour (UPT's vpt_embeddings_deep is computed and discarded there)."""
+        return self.modality == "image" and bool(getattr(self.config, "VPT_DEEP", False))
 
     def define_model(self, classes=None):
         c, dev = self.config, self.device
@@ -83,7 +90,9 @@ class TrainingStrategy:
         if self.modality == "text":
             self.model = TextPrefixModel(self.initial_prefix.clone().to(dev), self.text_encoder, classes, device=dev)
         elif self.modality == "image":
-            self.model = ImagePrefixModel(self.initial_prefix.clone().to(dev), self.image_encoder, device=dev)
+            deep = getattr(self, "initial_deep_prefix", None)
+            self.model = ImagePrefixModel(self.initial_prefix.clone().to(dev), self.image_encoder, device=dev,
+                                          deep_prefix=None if deep is None else deep.clone().to(dev))
         else:
             torch.manual_seed(int(getattr(c, "OPTIM_SEED", 0)))
             self.model = UPTModel(self.coop_init.clone().to(dev), self.vpt_init.clone().to(dev), None, self.image_encoder,
@@ -109,6 +118,8 @@ class TrainingStrategy:
 
     def prompt_snapshot(self):
         m = self.unwrap_model()
+        if self.modality == "image" and getattr(m, "deep_prefix", None) is not None:
+            return [m.prefix.detach().cpu().numpy(), m.deep_prefix.detach().cpu().numpy()]
         if self.modality in ("text", "image"):
             return [m.prefix.detach().cpu().numpy()]
         # multimodal_prompt.py:149-158 of the reference: the eight trainable pieces, positionally -- NOT the whole UPTModel
@@ -375,6 +386,11 @@ class TrainingStrategy:
         ids = self.text_encoder._token_ids(coop_embs.shape[1], classes)
         return text_prefix_forward(clip_model.text_tower, ids, coop_embs.detach()), vpt_embs.detach()
 
+    def deep_prompts(self):
+        """The visual model's trained deep prompts [D, P, d] (detached), or None."""
+        deep = getattr(self.model, "deep_prefix", None) if self.modality == "image" else None
+        return None if deep is None else deep.detach()
+
     @torch.no_grad()
     def trained_features(self, images, classes, chunk=440):
         """(image features [N, E] of the whole ordered pool, text features [C, E]) of the CURRENT model for the pseudolabel pass.
@@ -388,7 +404,7 @@ class TrainingStrategy:
             self.model.classes = classes
             return pl.encode_pool(tower, images, chunk=chunk), self.model(classes)
         if self.modality == "image":
-            return pl.encode_pool(tower, images, chunk=chunk, prefix=self.model.prefix.detach()), self.fixed_text_features(classes)
+            return pl.encode_pool(tower, images, chunk=chunk, prefix=self.model.prefix.detach(), deep=self.deep_prompts()), self.fixed_text_features(classes)
         self.model.classes = classes
         coop_embs, vpt_embs = self.model.mix()
         txt = self.model.text_encoder(coop_embs, classes)
@@ -408,7 +424,7 @@ class TrainingStrategy:
             txt, vprompt = self.trained_text_features(classes, twin)
             fp, lab = pl.identical_lists(self.clip_model.visual.tower, twin.visual.tower, images, txt, self.scale(),
                                          list(unlabeled_data.filepaths), labels, k, chunk=440, prefix=vprompt, argmax_on="logits",
-                                         visual_mid=pl.mid_tower(self.clip_model, len(unlabeled_data.filepaths)))
+                                         visual_mid=pl.mid_tower(self.clip_model, len(unlabeled_data.filepaths)), deep=self.deep_prompts())
         else:
             img, txt = self.trained_features(images, classes)
             fp, lab = pl.pseudolabel_from_features(img, txt, self.scale(), list(unlabeled_data.filepaths), labels, k, argmax_on="logits")

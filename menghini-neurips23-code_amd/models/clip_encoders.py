@@ -87,12 +87,16 @@ class CustomVisionTransformer(nn.Module):
         self.proj = vision_transformer.proj
         self._vt = [vision_transformer]
 
-    def forward(self, x, image_prefix, pos_emb=True, deep_embs=None):
+    def forward(self, x, image_prefix, pos_emb=True, deep_embs=None, deep_prompts=None):
+        """deep_prompts: None or [D, P, d] (1 <= D <= layers - 1) deep visual prompts: before block l (1 <= l <= D) the stream's prompt rows are
+        replaced by deep_prompts[l - 1], no LayerNorm and no positional embedding -- the reference's deep branch (:158-174) with its vpt_proj and
+        vpt_dropout as identity (a projection, if wanted, is applied by the caller before the call).  Differentiable, as image_prefix is."""
         if deep_embs is not None:
             # reference :158-174 reads self.visual / self.mvlpt_model, attributes this class never has: the branch raises
-            # AttributeError upstream as well (VPT_DEEP is False in every config)
-            raise NotImplementedError("deep prompts are unreachable in the reference (VPT_DEEP: False; :158-174 reads attributes that do not exist)")
-        return vit_prefix_forward(self._vt[0].tower, x, image_prefix, pos_emb=bool(pos_emb))   # :141
+            # AttributeError upstream as well (VPT_DEEP is False in every config).  The native form of deep prompts is `deep_prompts`.
+            raise NotImplementedError("deep prompts are unreachable in the reference (VPT_DEEP: False; :158-174 reads attributes that do not exist); "
+                                      "pass deep_prompts= for the engine's deep visual prompts")
+        return vit_prefix_forward(self._vt[0].tower, x, image_prefix, pos_emb=bool(pos_emb), deep=deep_prompts)   # :141
 
 
 class CustomImageEncoder(nn.Module):
@@ -103,5 +107,5 @@ class CustomImageEncoder(nn.Module):
         self.visual = CustomVisionTransformer(visual)
         self.dtype = self.visual.conv1.weight.dtype
 
-    def forward(self, image, prefix, deep_embds=None):
-        return self.visual(image, prefix, deep_embs=deep_embds)
+    def forward(self, image, prefix, deep_embds=None, deep_prompts=None):
+        return self.visual(image, prefix, deep_embs=deep_embds, deep_prompts=deep_prompts)

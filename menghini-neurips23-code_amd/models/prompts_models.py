@@ -44,15 +44,19 @@ class TextPrefixModel(_ModuleShim, nn.Module):
 
 
 class ImagePrefixModel(_ModuleShim, nn.Module):
-    def __init__(self, initial_prefix, image_encoder, temperature=0.07, device="cpu"):
+    def __init__(self, initial_prefix, image_encoder, temperature=0.07, device="cpu", deep_prefix=None):
         super().__init__()
         self.device = device
         self.initialized_prefix = initial_prefix
         self.prefix = nn.Parameter(initial_prefix)
         self.image_encoder = image_encoder
+        # VPT-Deep: [D, P, d] prompts replacing the prompt rows entering blocks 1 .. D (CustomVisionTransformer.forward(deep_prompts=))
+        self.deep_prefix = nn.Parameter(deep_prefix) if deep_prefix is not None else None
 
     def forward(self, x):
-        return self.image_encoder(x, self.prefix)          # un-normalised, as reference :55-61
+        if self.deep_prefix is None:
+            return self.image_encoder(x, self.prefix)          # un-normalised, as reference :55-61
+        return self.image_encoder(x, self.prefix, deep_prompts=self.deep_prefix)
 
 
 class UPTModel(_ModuleShim, nn.Module):

@@ -116,13 +116,13 @@ def note_screen_bound(key, stream, stats):
 
 
 @torch.no_grad()
-def encode_pool(visual_tower, images, chunk=880, prefix=None, out=None, screen=False):
+def encode_pool(visual_tower, images, chunk=880, prefix=None, out=None, screen=False, deep=None):
     """Encode an ordered pool.  `images` is a tensor [N,3,R,R] (any device) or a callable
     (lo, hi) -> tensor for that slice.  With torch.distributed initialised the pool is sharded
     contiguously and the embeddings are all-gathered; returns [N, E] f32 on the device.
     screen: False, or the stream form ("hilo" / "f16") of a screen-and-refine pass's screen; True = screen_stream() without a pool history.
     prefix: None, one visual prompt for the whole pool ([P, d] / [1, P, d]), or one per image ([N, P, d], aligned with `images`: each rank
-    reads the prompts of its own shard)."""
+    reads the prompts of its own shard).  deep: None or [D, P, d] deep prompts of a shared prompt (Tower.encode_chunks)."""
     if screen is True:
         screen = screen_stream()
     n = images.shape[0] if torch.is_tensor(images) else images.n
@@ -131,7 +131,7 @@ def encode_pool(visual_tower, images, chunk=880, prefix=None, out=None, screen=F
     lo, hi, per = gdist.shard_range(n)
     dev = visual_tower.device
     local = torch.empty(max(hi - lo, 0), visual_tower.embed_dim, dtype=torch.float32, device=dev)
-    visual_tower.encode_chunks(images, local, lo, hi, chunk, prefix, hilo=screen == "hilo")
+    visual_tower.encode_chunks(images, local, lo, hi, chunk, prefix, hilo=screen == "hilo", deep=deep)
     return gdist.allgather_rows(local, n, per, tag="pool_embeddings")
 
 
@@ -570,10 +570,11 @@ def balanced_chunk(n_rows, chunk):
     return max(1, -(-int(n_rows) // parts))
 
 
-def tier_rows(tower, fetch, txt, scale, n, lo, hi, chunk, prefix=None, argmax_on="probs", on_rows=None, timer=None):
+def tier_rows(tower, fetch, txt, scale, n, lo, hi, chunk, prefix=None, argmax_on="probs", on_rows=None, timer=None, deep=None):
     """A refinement tier as refine_scan's callback: rows(idx) -> (probs [len(idx), C], arg-max) of the global rows `idx` (ascending) re-encoded by `tower`.
     Each rank encodes the rows of its own shard [lo, hi) -- `fetch(global_rows)` returns their images -- and one padded all-gather assembles the rest.
     prefix: None, a shared visual prompt, or per-image prompts [n, P, d] aligned with the pool (the rows' own prompts go with them: take_prefix).
+    deep: None or the shared prompt's deep prompts [D, P, d] (every row alike).
     rows.submit(idx) only ENQUEUES the work, on the tier's own HIP stream, and returns the function that waits for it: two tiers submitted back to back
     (refine_scan does that wherever their row sets are independent) share the GPU instead of taking turns at small-batch efficiency."""
     dev = tower.device
@@ -588,7 +589,7 @@ def tier_rows(tower, fetch, txt, scale, n, lo, hi, chunk, prefix=None, argmax_on
             local = torch.empty(len(mine), tower.embed_dim, dtype=torch.float32, device=dev)
             if len(mine):
                 tower.encode_chunks(lambda a, b: fetch(mine[a:b]), local, 0, len(mine), balanced_chunk(len(mine), chunk), take_prefix(prefix, mine),
-                                    streams=tier_streams())
+                                    streams=tier_streams(), deep=deep)
             if on_rows is not None:
                 on_rows(len(mine))
             got = gdist.allgather_selected(local, idx, n, tag="refined_rows")
@@ -614,7 +615,7 @@ def tier_rows(tower, fetch, txt, scale, n, lo, hi, chunk, prefix=None, argmax_on
 
 @torch.no_grad()
 def identical_lists(visual16, visual32, images, txt_exact, scale, paths, class_labels, k, chunk=880, exact_chunk=880, prefix=None,
-                    argmax_on="probs", streams=2, emb16=None, visual_mid=None, mid_chunk=880):
+                    argmax_on="probs", streams=2, emb16=None, visual_mid=None, mid_chunk=880, deep=None):
     """(filepaths, labels) of the reference's fp32 pseudolabel scan (utils/clip_pseudolabels.py:24-112) at close to the f16
     towers' throughput: the whole pool goes through the f16 vision tower `visual16` (sharded over ranks, one all-gather), the
     head scores it against the EXACT text features `txt_exact`, and refine_scan re-encodes only the rows whose probabilities cannot
@@ -623,7 +624,8 @@ def identical_lists(visual16, visual32, images, txt_exact, scale, paths, class_l
     all-gather per round and tier).  The lists are the exact mode's lists provided every row obeys the measured bound of the tier it
     was left at; the bound is calibrated on this pool, audited on a hold-out sample after certification and reported in
     LAST_REFINE_STATS (asserted equal to the exact mode at N = 50 000 in tests/test_gpu_identical.py).  prefix: None, one visual prompt for
-    the pool, or one per image ([N, P, d]): every tier encodes a row with its own prompt."""
+    the pool, or one per image ([N, P, d]): every tier encodes a row with its own prompt.  deep: None or [D, P, d] deep prompts of a shared
+    prompt, given to the screen and to every tier alike."""
     global LAST_REFINE_STATS
     n = len(paths)
     if n == 0:
@@ -632,7 +634,7 @@ def identical_lists(visual16, visual32, images, txt_exact, scale, paths, class_l
         return [], []
     key = (id(visual16), n, len(class_labels))        # the pool as far as the screen's choice of stream goes (same tower, same size, same class count)
     stream = screen_stream(key) if emb16 is None else None
-    emb = emb16 if emb16 is not None else encode_pool(visual16, images, chunk=chunk, prefix=prefix, screen=stream)
+    emb = emb16 if emb16 is not None else encode_pool(visual16, images, chunk=chunk, prefix=prefix, screen=stream, deep=deep)
     dev = emb.device
     _, probs, am_l, am_p = engine.cosine_head(emb, txt_exact, scale)
     probs_h = probs.cpu().numpy()
@@ -643,7 +645,7 @@ def identical_lists(visual16, visual32, images, txt_exact, scale, paths, class_l
     def rows_through(tower, tier, tier_chunk):
         def count(m):
             encoded[tier] += m
-        return tier_rows(tower, lambda rows: take_images(images, rows), txt_exact, scale, n, lo, hi, tier_chunk, prefix, argmax_on, on_rows=count)
+        return tier_rows(tower, lambda rows: take_images(images, rows), txt_exact, scale, n, lo, hi, tier_chunk, prefix, argmax_on, on_rows=count, deep=deep)
 
     img, cls, stats = refine_scan(probs_h, pred_h, path_ranks(paths), k, rows_through(visual32, "exact", exact_chunk),
                                   mid_rows=rows_through(visual_mid, "mid", mid_chunk) if visual_mid is not None else None)

@@ -72,7 +72,8 @@ def vpt_step(model, text_features, logit_scale, images, labels, row_weight, opti
     image_features = model(images)
     logits = CosineHeadFn.apply(image_features, text_features, logit_scale)
     loss = WeightedCEFn.apply(logits, labels, row_weight)
-    return _finish(loss, [model.prefix], optimizer, logits if return_logits else None)
+    deep = getattr(model, "deep_prefix", None)      # VPT-Deep: its gradient is all-reduced with the prompt's
+    return _finish(loss, [model.prefix] if deep is None else [model.prefix, deep], optimizer, logits if return_logits else None)
 
 
 def upt_step(model, logit_scale, images, labels, row_weight, optimizer, return_logits=False):
@@ -307,14 +308,16 @@ def lookahead_image_features(clip_model, batches, group=8, overlap=None):
 
 class GraphedVptStep(GraphedStep):
     """vpt_step (visual prompt: image tower forward + backward; text features fixed for the epoch) replayed from a HIP graph.  The graph
-    captures a shared prompt ([P, d] / [1, P, d]); a model whose prompt is per image ([B, P, d]) runs the eager step."""
+    captures a shared prompt ([P, d] / [1, P, d]), with its deep prompts (VPT-Deep, model.deep_prefix [D, P, d]) as one more static parameter when
+    the model has them; a model whose prompt is per image ([B, P, d]) runs the eager step."""
 
     def __init__(self, model, text_features, logit_scale, optimizer):
         super().__init__(optimizer)
         self.model, self.text_features, self.scale = model, text_features, float(logit_scale)
 
     def params(self):
-        return [self.model.prefix]
+        deep = getattr(self.model, "deep_prefix", None)
+        return [self.model.prefix] if deep is None else [self.model.prefix, deep]
 
     def forward_logits(self):
         return CosineHeadFn.apply(self.model(self.x), self.text_features, self.scale)
