@@ -244,6 +244,22 @@ int grip_upt_mixer_forward(const grip_upt_mixer* m, float* coop_out, float* vpt_
 int grip_upt_mixer_backward(const grip_upt_mixer* m, const float* d_coop_out, const float* d_vpt_out, const grip_upt_mixer* grads,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* Deep UPT (ABI 9 additions; with n_deep = 0 these are the three calls above, bit for bit): UPTModel's vpt_embeddings_deep (models/prompts_models.py:69,
+ * :94-97) mixed with the prompts as :133-134 and :146 intend -- proj_vpt_pre(cat(vpt, vpt_deep)), the block over the sequence
+ * (coop, vpt, deep[0] .. deep[n_deep - 1]) of length S = 2 + n_deep (batch P), proj_vpt_post of the rows 1 .. S - 1.  The outputs feed the image
+ * tower's deep prompts (grip_vit_forward_deep).  Same struct, rounding points (half_linears) and determinism as the shallow mixer.
+ *   n_deep           0 .. 31
+ *   vpt_deep         [n_deep, P, vision_width]      the deep prompt embeddings (the backward takes the forward's values, as it does m->vpt)
+ *   vpt_deep_out     [n_deep, P, vision_width]      proj_vpt_post of the deep rows: the deep visual prompts of blocks 1 .. n_deep
+ *   d_vpt_deep_out   its gradient (grip_vit_backward_deep's grad_deep);  grad_vpt_deep [n_deep, P, vision_width] <- the deep embeddings' gradient
+ * The workspace of n_deep > 0 is larger: grip_upt_mixer_deep_workspace. */
+int grip_upt_mixer_deep_workspace(int n_prompt, int n_deep, int text_width, int vision_width, int dim, size_t* bytes);
+int grip_upt_mixer_forward_deep(const grip_upt_mixer* m, const float* vpt_deep, int n_deep, float* coop_out, float* vpt_out, float* vpt_deep_out,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int grip_upt_mixer_backward_deep(const grip_upt_mixer* m, const float* vpt_deep, int n_deep, const float* d_coop_out, const float* d_vpt_out,
+                                 const float* d_vpt_deep_out, const grip_upt_mixer* grads, float* grad_vpt_deep, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * CLIP preprocessing of one decoded image: the `_transform` the reference applies per item on the host
  * (data/dataset.py:64-79 via clip.load's preprocess): Resize(n_px, BICUBIC) -> CenterCrop(n_px) -> ToTensor -> Normalize.

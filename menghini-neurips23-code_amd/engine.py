@@ -540,7 +540,9 @@ class WeightedCEFn(torch.autograd.Function):
 
 class UptMixerFn(torch.autograd.Function):
     """UPTModel's prompt mixer (models/prompts_models.py:129-146) on the native kernels (csrc/mixer.hip): forward and the
-    gradients of all 22 tensors -- the two prompt embeddings, the four projections and the one-block transformer."""
+    gradients of all 22 tensors -- the two prompt embeddings, the four projections and the one-block transformer.  A 23rd tensor,
+    vpt_embeddings_deep [D, P, dv], makes it the deep mixer (grip_upt_mixer_*_deep: the sequence grows to 2 + D tokens); it then
+    returns (coop, vpt, vpt_deep) and that tensor's gradient too."""
 
     @staticmethod
     def forward(ctx, *tensors):
@@ -550,34 +552,53 @@ class UptMixerFn(torch.autograd.Function):
         P, dt, dv, D = coop.shape[0], coop.shape[1], vpt.shape[1], ts[2].shape[0]
         if vpt.shape[0] != P:
             raise native.GripError(f"UPT mixer: {P} text prompt tokens but {vpt.shape[0]} visual ones (the reference concatenates them along dim 0)")
+        deep = ts[22] if len(ts) > 22 else None
+        if deep is not None and (deep.dim() != 3 or tuple(deep.shape[1:]) != (P, dv)):
+            raise native.GripError(f"UPT mixer: vpt_embeddings_deep has shape {tuple(deep.shape)}, expected [D, {P}, {dv}]")
+        nd = 0 if deep is None else deep.shape[0]
         dev = coop.device
         nbytes = c_size_t()
-        native.check(lib.grip_upt_mixer_workspace(P, dt, dv, D, byref(nbytes)))
+        if deep is None:
+            native.check(lib.grip_upt_mixer_workspace(P, dt, dv, D, byref(nbytes)))
+        else:
+            native.check(lib.grip_upt_mixer_deep_workspace(P, nd, dt, dv, D, byref(nbytes)))
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
         coop_out = torch.empty(P, dt, dtype=torch.float32, device=dev)
         vpt_out = torch.empty(P, dv, dtype=torch.float32, device=dev)
         # the reference's float16 branch (multimodal_prompt.py:46): fp16 projection Linears / prompt embeddings around the fp32 block
         half = int(tensors[2].dtype == torch.float16)
-        m = native.UptMixer(P, dt, dv, D, half, 0, *[t.data_ptr() for t in ts])
-        native.check(lib.grip_upt_mixer_forward(byref(m), _ptr(coop_out), _ptr(vpt_out), _ptr(ws), ws.numel(), _stream()))
+        m = native.UptMixer(P, dt, dv, D, half, 0, *[t.data_ptr() for t in ts[:22]])
+        if deep is None:
+            native.check(lib.grip_upt_mixer_forward(byref(m), _ptr(coop_out), _ptr(vpt_out), _ptr(ws), ws.numel(), _stream()))
+            outs = (coop_out, vpt_out)
+        else:
+            deep_out = torch.empty(nd, P, dv, dtype=torch.float32, device=dev)
+            native.check(lib.grip_upt_mixer_forward_deep(byref(m), _ptr(deep), nd, _ptr(coop_out), _ptr(vpt_out), _ptr(deep_out), _ptr(ws), ws.numel(),
+                                                         _stream()))
+            outs = (coop_out, vpt_out, deep_out)
         ctx.save_for_backward(*ts)
-        ctx.ws, ctx.dims, ctx.half = ws, (P, dt, dv, D), half
+        ctx.ws, ctx.dims, ctx.half = ws, (P, dt, dv, D, nd), half
         ctx.shapes = [t.shape for t in tensors]
         ctx.dtypes = [t.dtype for t in tensors]
-        return coop_out, vpt_out
+        return outs
 
     @staticmethod
-    def backward(ctx, d_coop, d_vpt):
+    def backward(ctx, d_coop, d_vpt, d_deep=None):
         lib = native.lib()
         ts = ctx.saved_tensors
-        P, dt, dv, D = ctx.dims
+        P, dt, dv, D, nd = ctx.dims
         dev = ts[0].device
         d_coop = torch.zeros(P, dt, device=dev) if d_coop is None else d_coop.contiguous().float()
         d_vpt = torch.zeros(P, dv, device=dev) if d_vpt is None else d_vpt.contiguous().float()
         grads = [torch.empty_like(t) for t in ts]
-        m = native.UptMixer(P, dt, dv, D, ctx.half, 0, *[t.data_ptr() for t in ts])
-        g = native.UptMixer(P, dt, dv, D, ctx.half, 0, *[t.data_ptr() for t in grads])
-        native.check(lib.grip_upt_mixer_backward(byref(m), _ptr(d_coop), _ptr(d_vpt), byref(g), _ptr(ctx.ws), ctx.ws.numel(), _stream()))
+        m = native.UptMixer(P, dt, dv, D, ctx.half, 0, *[t.data_ptr() for t in ts[:22]])
+        g = native.UptMixer(P, dt, dv, D, ctx.half, 0, *[t.data_ptr() for t in grads[:22]])
+        if nd == 0:
+            native.check(lib.grip_upt_mixer_backward(byref(m), _ptr(d_coop), _ptr(d_vpt), byref(g), _ptr(ctx.ws), ctx.ws.numel(), _stream()))
+        else:
+            d_deep = torch.zeros(nd, P, dv, device=dev) if d_deep is None else d_deep.contiguous().float()
+            native.check(lib.grip_upt_mixer_backward_deep(byref(m), _ptr(ts[22]), nd, _ptr(d_coop), _ptr(d_vpt), _ptr(d_deep), byref(g), _ptr(grads[22]),
+                                                          _ptr(ctx.ws), ctx.ws.numel(), _stream()))
         return tuple(gr.reshape(sh).to(dtp) for gr, sh, dtp in zip(grads, ctx.shapes, ctx.dtypes))
 
 

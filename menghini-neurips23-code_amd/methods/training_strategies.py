@@ -78,11 +78,18 @@ class TrainingStrategy:
         else:
             self.coop_init = init(1, int(c.TEXT_PREFIX_SIZE), d.transformer_width)
             self.vpt_init = init(1, int(c.VISION_PREFIX_SIZE), d.vision_width)
+            # UPT_DEEP: vpt_embeddings_deep for blocks 1 .. layers - 1, drawn after the two prompts (which stay bit-identical with and without it)
+            self.vpt_deep_init = init(d.vision_layers - 1, int(c.VISION_PREFIX_SIZE), d.vision_width) if self.upt_deep() else None
 
     def vpt_deep(self):
-        """Deep visual prompts (VPT-Deep) for the visual strategies: config VPT_DEEP, default False.  The multimodal strategies keep the reference's
-        behaviour (UPT's vpt_embeddings_deep is computed and discarded there)."""
+        """Deep visual prompts (VPT-Deep) for the visual strategies: config VPT_DEEP, default False.  The multimodal strategies ignore it, as the
+        reference does (its UPT computes vpt_embeddings_deep and discards it); they have UPT_DEEP."""
         return self.modality == "image" and bool(getattr(self.config, "VPT_DEEP", False))
+
+    def upt_deep(self):
+        """Deep UPT for the multimodal strategies: config UPT_DEEP, default False.  UPTModel(mix_deep=True) mixes vpt_embeddings_deep with the
+        prompts and feeds its outputs to the image tower as deep prompts."""
+        return self.modality == "multi" and bool(getattr(self.config, "UPT_DEEP", False))
 
     def define_model(self, classes=None):
         c, dev = self.config, self.device
@@ -95,8 +102,10 @@ class TrainingStrategy:
                                           deep_prefix=None if deep is None else deep.clone().to(dev))
         else:
             torch.manual_seed(int(getattr(c, "OPTIM_SEED", 0)))
-            self.model = UPTModel(self.coop_init.clone().to(dev), self.vpt_init.clone().to(dev), None, self.image_encoder,
-                                  self.text_encoder, classes, int(getattr(c, "TRANSFORMER_DIM", 128)), device=dev, dtype=torch.float32)
+            deep = getattr(self, "vpt_deep_init", None)
+            self.model = UPTModel(self.coop_init.clone().to(dev), self.vpt_init.clone().to(dev), None if deep is None else deep.clone().to(dev),
+                                  self.image_encoder, self.text_encoder, classes, int(getattr(c, "TRANSFORMER_DIM", 128)), device=dev,
+                                  dtype=torch.float32, mix_deep=deep is not None)
         params = [p for p in self.model.parameters() if p.requires_grad]
         self.optimizer = torch.optim.SGD(params, lr=float(c.LR), weight_decay=float(c.DECAY), momentum=float(getattr(c, "MOMENTUM", 0.0)))
         self.scheduler = make_scheduler(self.optimizer, c)
@@ -382,13 +391,18 @@ class TrainingStrategy:
             return text_prefix_forward(clip_model.text_tower, ids, self.model.prefix.detach()), None
         if self.modality == "image":
             return clip_model.encode_text(clip.tokenize(self.text_prompts(classes)).to(self.device)), self.model.prefix.detach()
-        coop_embs, vpt_embs = self.model.mix()
+        coop_embs, vpt_embs = self.model.mix()[:2]
         ids = self.text_encoder._token_ids(coop_embs.shape[1], classes)
         return text_prefix_forward(clip_model.text_tower, ids, coop_embs.detach()), vpt_embs.detach()
 
+    @torch.no_grad()
     def deep_prompts(self):
-        """The visual model's trained deep prompts [D, P, d] (detached), or None."""
-        deep = getattr(self.model, "deep_prefix", None) if self.modality == "image" else None
+        """The trained deep prompts [D, P, d] the image tower reads (detached), or None: the visual model's deep_prefix, or the deep rows of
+        the UPT mixer's output (deep UPT; the mixer is deterministic, so this is the tensor the model's own forward feeds the tower)."""
+        if self.modality == "image":
+            deep = getattr(self.model, "deep_prefix", None)
+        else:
+            deep = self.model.mix()[2] if self.modality == "multi" and getattr(self.model, "mix_deep", False) else None
         return None if deep is None else deep.detach()
 
     @torch.no_grad()
@@ -406,9 +420,9 @@ class TrainingStrategy:
         if self.modality == "image":
             return pl.encode_pool(tower, images, chunk=chunk, prefix=self.model.prefix.detach(), deep=self.deep_prompts()), self.fixed_text_features(classes)
         self.model.classes = classes
-        coop_embs, vpt_embs = self.model.mix()
+        coop_embs, vpt_embs, *deep = self.model.mix()
         txt = self.model.text_encoder(coop_embs, classes)
-        return pl.encode_pool(tower, images, chunk=chunk, prefix=vpt_embs.detach()), txt
+        return pl.encode_pool(tower, images, chunk=chunk, prefix=vpt_embs.detach(), deep=deep[0].detach() if deep else None), txt
 
     @torch.no_grad()
     def assign_pseudo_labels(self, k, unlabeled_data):

@@ -61,7 +61,7 @@ class ImagePrefixModel(_ModuleShim, nn.Module):
 
 class UPTModel(_ModuleShim, nn.Module):
     def __init__(self, coop_embeddings, vpt_embeddings, vpt_embeddings_deep, image_encoder, text_encoder, classes,
-                 dim_transformer, temperature=0.07, device="cpu", dtype=torch.float32):
+                 dim_transformer, temperature=0.07, device="cpu", dtype=torch.float32, mix_deep=False):
         super().__init__()
         self.device = device
         self.classes = classes
@@ -72,6 +72,11 @@ class UPTModel(_ModuleShim, nn.Module):
         self.coop_length, self.coop_dim = self.coop_embeddings.size()[1], self.coop_embeddings.size()[2]
         self.vpt_length, self.vpt_dim = self.vpt_embeddings.size()[1], self.vpt_embeddings.size()[2]
         self.vpt_embeddings_deep = nn.Parameter(vpt_embeddings_deep) if vpt_embeddings_deep is not None else None
+        # deep UPT: vpt_embeddings_deep [D, P, dv] joins the mixer's sequence and its outputs become the image tower's deep prompts (what :133-134
+        # and :146 intend; upstream :135 and :150 discard them).  Off (the default), a given vpt_embeddings_deep is ignored, as upstream.
+        if mix_deep and self.vpt_embeddings_deep is None:
+            raise ValueError("UPTModel(mix_deep=True) needs vpt_embeddings_deep [D, P, vision_width]")
+        self.mix_deep = bool(mix_deep)
         self.proj_coop_pre = nn.Linear(self.coop_dim, dim_transformer, dtype=self.dtype).to(self.device)
         self.proj_coop_post = nn.Linear(dim_transformer, self.coop_dim, dtype=self.dtype).to(self.device)
         self.proj_vpt_pre = nn.Linear(self.vpt_dim, dim_transformer, dtype=self.dtype).to(self.device)
@@ -83,37 +88,49 @@ class UPTModel(_ModuleShim, nn.Module):
     def _native_mixer_ok(self):
         """The native mixer covers what the reference builds (:99-119): one block, one head, on the GPU, float32 -- or the float16 branch
         of multimodal_prompt.py:46 (fp16 prompt embeddings and projection Linears around the fp32 block: the same kernels with fp16 rounding
-        points, grip_upt_mixer.half_linears).  Any other shape runs the same arithmetic through the framework's kernels."""
+        points, grip_upt_mixer.half_linears) -- with up to 31 deep prompts [D, P, dv] when mix_deep is on.  Any other shape runs the same
+        arithmetic through the framework's kernels."""
         import os
         t = self.transformer
         dtypes_ok = all(p.dtype == self.dtype for p in (self.coop_embeddings, self.vpt_embeddings, self.proj_coop_pre.weight, self.proj_vpt_post.weight)) \
             and t.resblocks[0].ln_1.weight.dtype == torch.float32
+        if self.mix_deep:
+            d = self.vpt_embeddings_deep
+            dtypes_ok = dtypes_ok and d.dtype == self.dtype and d.is_cuda and d.dim() == 3 and 1 <= d.shape[0] <= 31 \
+                and tuple(d.shape[1:]) == (self.vpt_length, self.vpt_dim)
         return (self.dtype in (torch.float32, torch.float16) and dtypes_ok and self.coop_embeddings.is_cuda and os.environ.get("GRIP_NATIVE_MIXER", "1") != "0"
                 and getattr(t, "layers", 0) == 1 and t.resblocks[0].attn.num_heads == 1 and len(self.coop_embeddings) == 1
                 and self.coop_length == self.vpt_length and self.coop_length <= 16 and t.width % 64 == 0 and t.width <= 256)
 
     def mix(self):
-        """Reference :129-146 (incl. the fp32 -> fp16 -> dtype round trip of :138-145)."""
+        """Reference :129-146 (incl. the fp32 -> fp16 -> dtype round trip of :138-145): (coop_embs, vpt_embs), and with mix_deep
+        (coop_embs, vpt_embs, deep_embs [D, P, dv]) -- the visual rows of the mixer's output split into the shallow prompt and the deep ones."""
+        deep = self.vpt_embeddings_deep if self.mix_deep else None
         if self._native_mixer_ok():
             from ..engine import UptMixerFn
             b = self.transformer.resblocks[0]
-            coop_embs, vpt_embs = UptMixerFn.apply(
+            outs = UptMixerFn.apply(
                 self.coop_embeddings, self.vpt_embeddings, self.proj_coop_pre.weight, self.proj_coop_pre.bias, self.proj_vpt_pre.weight,
                 self.proj_vpt_pre.bias, b.ln_1.weight, b.ln_1.bias, b.attn.in_proj_weight, b.attn.in_proj_bias, b.attn.out_proj.weight,
                 b.attn.out_proj.bias, b.ln_2.weight, b.ln_2.bias, b.mlp.c_fc.weight, b.mlp.c_fc.bias, b.mlp.c_proj.weight, b.mlp.c_proj.bias,
-                self.proj_coop_post.weight, self.proj_coop_post.bias, self.proj_vpt_post.weight, self.proj_vpt_post.bias)
-            return (coop_embs.reshape(-1, self.coop_length, self.coop_dim).to(self.dtype), vpt_embs.reshape(-1, self.vpt_length, self.vpt_dim).to(self.dtype))
+                self.proj_coop_post.weight, self.proj_coop_post.bias, self.proj_vpt_post.weight, self.proj_vpt_post.bias, *([] if deep is None else [deep]))
+            return tuple(o.reshape(-1, n, d).to(self.dtype) for o, n, d in zip(outs, (self.coop_length, self.vpt_length, self.vpt_length),
+                                                                               (self.coop_dim, self.vpt_dim, self.vpt_dim)))
         coop = self.proj_coop_pre(self.coop_embeddings)
-        vpt = self.proj_vpt_pre(self.vpt_embeddings)
+        vpt = self.proj_vpt_pre(self.vpt_embeddings if deep is None else torch.cat((self.vpt_embeddings, deep), dim=0))
         seq = torch.cat((coop, vpt), dim=0).to(torch.float32)
         out = self.transformer(seq).to(torch.float16)
         n = len(self.coop_embeddings)
         coop_embs = self.proj_coop_post(out[:n].to(self.dtype)).reshape(-1, self.coop_length, self.coop_dim)
         vpt_embs = self.proj_vpt_post(out[n:].to(self.dtype)).reshape(-1, self.vpt_length, self.vpt_dim)
-        return coop_embs, vpt_embs
+        if deep is None:
+            return coop_embs, vpt_embs
+        nv = len(self.vpt_embeddings)
+        return coop_embs, vpt_embs[:nv], vpt_embs[nv:]
 
     def forward(self, x, classes):
-        coop_embs, vpt_embs = self.mix()
+        coop_embs, vpt_embs, *deep = self.mix()
+        kw = {"deep_prompts": deep[0]} if deep else {}
         if x.is_cuda:
             # the two towers are independent until the head: the image tower (forward and, through autograd's
             # stream tracking, its backward) runs on a side stream next to the text tower
@@ -121,12 +138,14 @@ class UPTModel(_ModuleShim, nn.Module):
             side = _side_stream(x.device)
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                visual_out = self.image_encoder(x, vpt_embs)
+                visual_out = self.image_encoder(x, vpt_embs, **kw)
             vpt_embs.record_stream(side)
+            if deep:
+                deep[0].record_stream(side)
             text_out = self.text_encoder(coop_embs, classes)
             main.wait_stream(side)
             visual_out.record_stream(main)
             return text_out, visual_out
         text_out = self.text_encoder(coop_embs, classes)
-        visual_out = self.image_encoder(x, vpt_embs)
+        visual_out = self.image_encoder(x, vpt_embs, **kw)
         return text_out, visual_out

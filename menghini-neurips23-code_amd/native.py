@@ -68,6 +68,11 @@ _SIGS = {
     "grip_upt_mixer_workspace": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
     "grip_upt_mixer_forward": (c_int, [POINTER(UptMixer), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "grip_upt_mixer_backward": (c_int, [POINTER(UptMixer), c_void_p, c_void_p, POINTER(UptMixer), c_void_p, c_size_t, c_void_p]),
+    # (ABI 9 additions) deep UPT: vpt_embeddings_deep [n_deep, P, vision_width] joins the mixer's sequence
+    "grip_upt_mixer_deep_workspace": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "grip_upt_mixer_forward_deep": (c_int, [POINTER(UptMixer), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "grip_upt_mixer_backward_deep": (c_int, [POINTER(UptMixer), c_void_p, c_int, c_void_p, c_void_p, c_void_p, POINTER(UptMixer), c_void_p, c_void_p, c_size_t,
+                                             c_void_p]),
     "grip_preprocess_image": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                       c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "grip_preprocess_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

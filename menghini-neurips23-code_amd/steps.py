@@ -333,7 +333,8 @@ class GraphedVptStep(GraphedStep):
 
 
 class GraphedUptStep(GraphedStep):
-    """upt_step (multimodal prompt: mixer + both towers forward and backward, towers on two streams) replayed from a HIP graph."""
+    """upt_step (multimodal prompt: mixer + both towers forward and backward, towers on two streams) replayed from a HIP graph.  Every trainable
+    parameter is captured, vpt_embeddings_deep included: with mix_deep (deep UPT) the graph holds the deep mixer and the tower's deep prompts."""
 
     def __init__(self, model, logit_scale, optimizer):
         super().__init__(optimizer)
