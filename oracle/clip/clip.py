@@ -50,11 +50,16 @@ def tokenize(texts, context_length: int = 77, truncate: bool = False):
     return out
 
 
-def build_model(name: str, seed: int = 0) -> CLIP:
+def build_model(name: str, seed: int = 0, fp16_grid: bool = False) -> CLIP:
+    """fp16_grid=True: the matrix weights rounded to f16 numbers (grip_amd.weights.on_f16_grid), what a published fp16 checkpoint holds and the
+    product's clip.load(..., fp16_checkpoint=True) builds.  The keyword is the only switch: the oracle does not read GRIP_SYNTHETIC_FP16."""
     d = _cfg.get_dims(name)
     m = CLIP(d.embed_dim, d.image_resolution, d.vision_layers, d.vision_width, d.vision_patch_size,
              d.context_length, d.vocab_size, d.transformer_width, d.transformer_heads, d.transformer_layers)
-    sd = {k: torch.from_numpy(v) for k, v in _weights.init_state_dict(d, seed).items()}
+    sd = _weights.init_state_dict(d, seed)
+    if fp16_grid:
+        sd = _weights.on_f16_grid(sd)
+    sd = {k: torch.from_numpy(v) for k, v in sd.items()}
     missing, unexpected = m.load_state_dict(sd, strict=False)
     assert not unexpected, unexpected
     assert not [k for k in missing if "attn_mask" not in k], missing
@@ -68,8 +73,8 @@ def _transform(n_px):
     return t
 
 
-def load(name: str, device="cpu", jit: bool = False, download_root=None, seed: int = 0):
-    m = build_model(name, seed)
+def load(name: str, device="cpu", jit: bool = False, download_root=None, seed: int = 0, fp16_grid: bool = False):
+    m = build_model(name, seed, fp16_grid)
     for p in m.parameters():
         p.requires_grad_(False)
     return m.to(device), _transform(m.visual.input_resolution)

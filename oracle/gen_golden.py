@@ -6,6 +6,7 @@ files) on top of the CPU oracle `clip` stand-in (oracle/clip), checks the oracle
 small fixtures (inputs regenerated from seeds; outputs stored) to tests/golden/.
 
     python oracle/gen_golden.py          # rewrites tests/golden/*
+    python oracle/gen_golden.py vitb16grid   # by request only: tests/golden/golden_vitb16_fp16grid.npz (the g3 block on the on-grid oracle)
 
 Nothing under tests/, bench.py or smoke() reads /root/reference at run time.
 """
@@ -49,8 +50,8 @@ def close(a, b, what, tol=1e-5):
 
 
 # ----------------------------------------------------------------------------- G1 / G2 / G4 / G5
-def towers(model_name, n_img, classes, P, tag, out, with_grad=True):
-    m, _ = clip.load(model_name)
+def towers(model_name, n_img, classes, P, tag, out, with_grad=True, fp16_grid=False):
+    m, _ = clip.load(model_name, fp16_grid=fp16_grid)
     d = grip_amd.config.get_dims(model_name)
     R = d.image_resolution
     x = T(f"{tag}.x", (n_img, 3, R, R))
@@ -259,7 +260,7 @@ def fpl_losses(out):
 
 
 def main():
-    """python oracle/gen_golden.py [small] [vitb16] [vitb32] [vitl14] [leaderboard]   (no argument = all groups)"""
+    """python oracle/gen_golden.py [small] [vitb16] [vitb32] [vitl14] [leaderboard]   (no argument = all of these groups; `vitb16grid` only when named)"""
     os.makedirs(OUT, exist_ok=True)
     cbind.build()
     groups = set(sys.argv[1:]) or {"small", "vitb16", "vitb32", "vitl14", "leaderboard"}
@@ -280,6 +281,13 @@ def main():
         towers("ViT-B/16", 2, classes[:3], 16, "g3", big, with_grad=True)
         upt("ViT-B/16", 2, classes[:3], 4, "g4b", big)
         np.savez_compressed(os.path.join(OUT, "golden_vitb16.npz"), **big)
+
+    if "vitb16grid" in groups:
+        # the g3 block again, same inputs and key names, on the oracle whose matrix weights are f16 numbers (clip.load(..., fp16_grid=True)): what the
+        # product's fp16_checkpoint=True towers are held to
+        grid = {}
+        towers("ViT-B/16", 2, classes[:3], 16, "g3", grid, with_grad=True, fp16_grid=True)
+        np.savez_compressed(os.path.join(OUT, "golden_vitb16_fp16grid.npz"), **grid)
 
     if "vitb32" in groups:
         # ViT-B/32: the encoder every shipped script of the reference defaults to (scripts/run_pseudolabels_ssl.sh:4): patch 32
