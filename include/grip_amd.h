@@ -183,10 +183,30 @@ int grip_text_forward(grip_tower* t, const int32_t* token_ids, const int32_t* eo
                       int n_prefix, int prefix_classes, int n_class, int seq_len, float* out_emb,
                       void* workspace, size_t workspace_bytes, int flags, uint64_t* generation, void* stream);
 
+/* Deep text prompts (deep CoOp, the language half of MaPLe-style deep prompting; ABI 9 addition -- grip_text_forward is this call with deep = NULL, n_deep = 0,
+ * and runs exactly as before):
+ *   deep       [n_deep, prefix_classes, n_prefix, width] f32.  Before block l (1 <= l <= n_deep) the positions 1 .. n_prefix of every class's residual stream
+ *              are replaced by deep[l - 1] (class c reads deep[l - 1][c], or deep[l - 1][0] when prefix_classes == 1): no LayerNorm, no positional and no
+ *              token embedding.  Block 0 reads the shallow context as above.  The replaced rows are again the same for every class when the context is
+ *              shared and the mask is causal, so GRIP_FWD_SHARED_PREFIX stays valid: the shared layout writes the n_prefix rows once.
+ *   n_deep     0 .. layers - 1; n_deep > 0 needs n_prefix > 0 and deep != NULL, and is refused on a vision tower (grip_vit_forward_deep is its call).
+ * Every tower precision, flag and legal seq_len otherwise as grip_text_forward.  A train-mode forward records n_deep: its backward is
+ * grip_text_backward_deep (grip_text_backward_prefix then fails with GRIP_ERR_STATE). */
+int grip_text_forward_deep(grip_tower* t, const int32_t* token_ids, const int32_t* eot_index, const float* prefix,
+                           int n_prefix, int prefix_classes, const float* deep, int n_deep, int n_class, int seq_len, float* out_emb,
+                           void* workspace, size_t workspace_bytes, int flags, uint64_t* generation, void* stream);
+
 /* grad_emb [n_class, embed_dim] -> grad_prefix [prefix_classes, n_prefix, width] (summed over classes
  * when prefix_classes == 1). */
 int grip_text_backward_prefix(grip_tower* t, const float* grad_emb, float* grad_prefix,
                               void* workspace, size_t workspace_bytes, uint64_t generation, void* stream);
+
+/* The same after grip_text_forward_deep (ABI 9 addition): grad_prefix as grip_text_backward_prefix, and grad_deep [n_deep, prefix_classes, n_prefix, width] f32 --
+ * grad_deep[l - 1] is the gradient of the stream rows 1 .. n_prefix entering block l, summed over the classes in class order when prefix_classes == 1, each
+ * class's own otherwise (no atomics: the same bits on every run).  Those rows get no gradient below block l (they were overwritten), so the shallow
+ * context's gradient flows through block 0 alone.  After a forward without deep prompts grad_deep is not touched (may be NULL). */
+int grip_text_backward_deep(grip_tower* t, const float* grad_emb, float* grad_prefix, float* grad_deep,
+                            void* workspace, size_t workspace_bytes, uint64_t generation, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Cosine x logit-scale head + softmax + argmax: the block inlined 45 times in the reference, e.g.

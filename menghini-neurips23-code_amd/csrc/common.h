@@ -225,6 +225,10 @@ int launch_vit_assemble_ln(const float* patch_out, const float* cls, const float
 // deep visual prompts: rows (b, 1 .. P) of the stream entering a block := deep [P, d] for every image; x_lo / stat_part / rowstat (each optional):
 // the compensated stream's lo parts and the row statistics of the values as stored (stat_part [d/64, M, 2] partial pairs, rowstat [M, 2] finalised)
 int launch_vit_deep_insert(const float* deep, void* x, int f32, half_t* x_lo, float* stat_part, float* rowstat, int B, int S, int P, int M, int d, hipStream_t s);
+// deep text context (grip_text_forward_deep): the same kernel, rows seq_row(c, 1 .. P, S, shared_rows) := deep[c or 0] -- deep [prefix_classes, P, d]; the shared-prefix
+// layout (shared_rows = P + 1, prefix_classes = 1) writes its P rows once.  (seq_row is declared below; M = rows of the stream)
+int launch_text_deep_insert(const float* deep, int prefix_classes, void* x, int f32, float* stat_part, float* rowstat, int C, int S, int P, int shared_rows, int M, int d,
+                            hipStream_t s);
 // rowstat [M, 2] = (mean, rstd) of every row from the [M, parts, 2] partial sums the residual GEMM epilogues emit
 int launch_ln_stats_finalize(const float* stat_part, int parts, float* rowstat, int M, int d, hipStream_t s);
 // W' = f16(gamma o W) [N, K]; colsum[n] = sum_k W'[n][k]; bias_out[n] = bias[n] + sum_k beta[k] W[n][k]
@@ -287,4 +291,6 @@ int launch_vit_prefix_grad(const float* dx, const float* prefix, const float* ga
 int launch_vit_deep_grad(float* dx, half_t* dxh, const float* scale, float* grad, int B, int S, int P, int d, hipStream_t s);
 int launch_vit_prefix_grad_per_image(const float* dx, const float* prefix, const float* gamma, const float* scale, float* grad, int B, int S, int P, int d, hipStream_t s);
 int launch_text_prefix_grad(const float* dx, const float* scale, float* grad, int C, int T, int P, int prefix_classes, int d, hipStream_t s);
+// deep text context: grad [prefix_classes, P, d] as launch_text_prefix_grad (class sum in class order when prefix_classes == 1), then the rows read := 0 in dx and dxh
+int launch_text_deep_grad(float* dx, half_t* dxh, const float* scale, float* grad, int C, int T, int P, int prefix_classes, int d, hipStream_t s);
 int launch_grad_scale_cast(const float* g, half_t* g16, float* scale, int n, hipStream_t s);

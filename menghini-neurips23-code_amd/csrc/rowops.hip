@@ -156,17 +156,21 @@ int launch_vit_assemble_ln(const float* patch_out, const float* cls, const float
 // epilogue's convention (gemm.hip EPI_BIAS_RESID_STATS): per 64-column tile (sum, sum of squares), laid out [d/64][M] in stat_part (train-mode
 // forwards, whose consumer adds the pairs itself), or those pairs added in tile order into (mean, rstd) with ln_stats_finalize's arithmetic (rowstat).
 // One wave per (image, prompt token) row.
+// The text tower's deep context (grip_text_forward_deep) runs the same kernel with B = classes: destination row seq_row(b, 1 + p, S, Ps), which is the
+// row above in the plain layout (Ps = 0) and row 1 + p once in the shared-prefix layout (launched with B = 1); class b reads deep + b * cstride
+// (cstride = P * d for a class-specific context, 0 for a shared one and on the vision tower).
 template <int NV, typename RT>
 __global__ __launch_bounds__(256) void vit_deep_insert_kernel(const float* __restrict__ deep, RT* __restrict__ x, half_t* __restrict__ x_lo,
-                                                              float* __restrict__ stat_part, float* __restrict__ rowstat, int B, int S, int P, int M, int d) {
+                                                              float* __restrict__ stat_part, float* __restrict__ rowstat, int B, int S, int P, int M, int d,
+                                                              int Ps, size_t cstride) {
 #pragma clang fp contract(off)      // (the statistics round as ln_stats_finalize's do)
     const int lane = threadIdx.x & 63;
     const int idx = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (idx >= B * P) return;
     const int b = idx / P, p = idx - b * P;
-    const size_t row = (size_t)b * S + 1 + p;
+    const size_t row = seq_row(b, 1 + p, S, Ps);
     const int d4 = d >> 2;
-    const f32x4* src = (const f32x4*)(deep + (size_t)p * d);
+    const f32x4* src = (const f32x4*)(deep + (size_t)b * cstride + (size_t)p * d);
     f32x4 v[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i)
@@ -212,18 +216,33 @@ __global__ __launch_bounds__(256) void vit_deep_insert_kernel(const float* __res
     }
 }
 
-int launch_vit_deep_insert(const float* deep, void* x, int f32, half_t* x_lo, float* stat_part, float* rowstat, int B, int S, int P, int M, int d, hipStream_t s) {
-    GRIP_REQUIRE(B > 0 && P > 0 && S >= 1 + P && M >= B * S, "vit_deep_insert: bad shape (B=%d P=%d S=%d M=%d)", B, P, S, M);
-    GRIP_REQUIRE(!(stat_part || rowstat) || (d % 64 == 0 && !f32), "vit_deep_insert: row statistics need an f16 stream of width %% 64 == 0 (width %d)", d);
+static int deep_insert(const char* who, const float* deep, size_t cstride, void* x, int f32, half_t* x_lo, float* stat_part, float* rowstat, int B, int S, int P, int Ps,
+                       int M, int d, hipStream_t s) {
+    GRIP_REQUIRE(deep && x && B > 0 && P > 0 && S >= 1 + P && (Ps == 0 ? M >= B * S : (Ps == P + 1 && B == 1 && M >= Ps)), "%s: bad shape (B=%d P=%d S=%d M=%d shared rows=%d)",
+                 who, B, P, S, M, Ps);
+    GRIP_REQUIRE(!(stat_part || rowstat) || (d % 64 == 0 && !f32), "%s: row statistics need an f16 stream of width %% 64 == 0 (width %d)", who, d);
     const int rows = B * P;
     if (f32) {
-        GRIP_REQUIRE(!x_lo && !stat_part && !rowstat, "vit_deep_insert: the f32 stream carries no lo part or statistics");
-        DISPATCH_NV(d, hipLaunchKernelGGL((vit_deep_insert_kernel<NV, float>), dim3((rows + 3) / 4), dim3(256), 0, s, deep, (float*)x, (half_t*)nullptr, stat_part, rowstat, B, S, P, M, d));
+        GRIP_REQUIRE(!x_lo && !stat_part && !rowstat, "%s: the f32 stream carries no lo part or statistics", who);
+        DISPATCH_NV(d, hipLaunchKernelGGL((vit_deep_insert_kernel<NV, float>), dim3((rows + 3) / 4), dim3(256), 0, s, deep, (float*)x, (half_t*)nullptr, stat_part, rowstat, B, S, P, M, d,
+                                          Ps, cstride));
     } else {
-        DISPATCH_NV(d, hipLaunchKernelGGL((vit_deep_insert_kernel<NV, resid_t>), dim3((rows + 3) / 4), dim3(256), 0, s, deep, (resid_t*)x, x_lo, stat_part, rowstat, B, S, P, M, d));
+        DISPATCH_NV(d, hipLaunchKernelGGL((vit_deep_insert_kernel<NV, resid_t>), dim3((rows + 3) / 4), dim3(256), 0, s, deep, (resid_t*)x, x_lo, stat_part, rowstat, B, S, P, M, d,
+                                          Ps, cstride));
     }
     GRIP_CHECK_HIP(hipGetLastError());
     return GRIP_OK;
+}
+
+int launch_vit_deep_insert(const float* deep, void* x, int f32, half_t* x_lo, float* stat_part, float* rowstat, int B, int S, int P, int M, int d, hipStream_t s) {
+    return deep_insert("vit_deep_insert", deep, 0, x, f32, x_lo, stat_part, rowstat, B, S, P, 0, M, d, s);
+}
+
+int launch_text_deep_insert(const float* deep, int prefix_classes, void* x, int f32, float* stat_part, float* rowstat, int C, int S, int P, int shared_rows, int M, int d,
+                            hipStream_t s) {
+    GRIP_REQUIRE(prefix_classes == 1 || (prefix_classes == C && shared_rows == 0), "text_deep_insert: prefix_classes must be 1 or n_class (plain layout); got %d for %d classes", prefix_classes, C);
+    // shared-prefix layout: the P rows exist once; plain layout: one set per class
+    return deep_insert("text_deep_insert", deep, prefix_classes == 1 ? 0 : (size_t)P * d, x, f32, nullptr, stat_part, rowstat, shared_rows ? 1 : C, S, P, shared_rows, M, d, s);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -309,8 +309,12 @@ __global__ __launch_bounds__(256) void vit_prefix_grad_per_image_kernel(const fl
 
 // Textual prompt slice: grad_prefix[pc][p] = inv_scale * sum_{c in group} dx[c*T + 1 + p]
 // One wave per (prompt token, 256-float slice of the row): a shared prompt sums C rows in class order, sixteen loads in flight.
+// ZERO: a deep context's slice (grip_text_backward_deep) -- the forward overwrote these stream rows before the block below, so once summed they are
+// zeroed in dx and dxh: nothing of them flows on.  Every element of those rows is read by exactly one lane, the one that then clears it (no race, no
+// atomics; the same adds in the same order as the shallow slice).
+template <bool ZERO = false>
 __global__ __launch_bounds__(256) void text_prefix_grad_kernel(const float* __restrict__ dx, const float* __restrict__ scale, float* __restrict__ grad,
-                                                               int C, int T, int P, int prefix_classes, int d) {
+                                                               int C, int T, int P, int prefix_classes, int d, half_t* __restrict__ dxh = nullptr) {
     const int lane = threadIdx.x & 63;
     const int d4 = d >> 2;
     const int nf = (d4 + 63) >> 6;
@@ -335,6 +339,14 @@ __global__ __launch_bounds__(256) void text_prefix_grad_kernel(const float* __re
         acc = ((const f32x4*)(dx + ((size_t)pc * T + 1 + p) * d))[f];
     }
     ((f32x4*)(grad + (size_t)idx * d))[f] = acc * inv;
+    if constexpr (ZERO) {
+        const int c0 = prefix_classes == 1 ? 0 : pc, c1 = prefix_classes == 1 ? C : pc + 1;
+        for (int c = c0; c < c1; ++c) {
+            const size_t o = ((size_t)c * T + 1 + p) * d;
+            ((f32x4*)((float*)dx + o))[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            ((half4*)(dxh + o))[f] = (half4){(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
+        }
+    }
 }
 
 // Dynamic loss scale: scale[0] = 2^k with amax(g) * 2^k in [32, 64), scale[1] = 2^-k; g16 = f16(g * scale).
@@ -466,7 +478,15 @@ int launch_vit_prefix_grad_per_image(const float* dx, const float* prefix, const
 }
 int launch_text_prefix_grad(const float* dx, const float* scale, float* grad, int C, int T, int P, int prefix_classes, int d, hipStream_t s) {
     const int waves = prefix_classes * P * ((d / 4 + 63) / 64);
-    hipLaunchKernelGGL(text_prefix_grad_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, dx, scale, grad, C, T, P, prefix_classes, d);
+    hipLaunchKernelGGL(text_prefix_grad_kernel<>, dim3((waves + 3) / 4), dim3(256), 0, s, dx, scale, grad, C, T, P, prefix_classes, d, (half_t*)nullptr);
+    GRIP_CHECK_HIP(hipGetLastError());
+    return GRIP_OK;
+}
+int launch_text_deep_grad(float* dx, half_t* dxh, const float* scale, float* grad, int C, int T, int P, int prefix_classes, int d, hipStream_t s) {
+    GRIP_REQUIRE(dx && dxh && grad && C > 0 && P > 0 && T > 1 + P && d % 4 == 0 && (prefix_classes == 1 || prefix_classes == C),
+                 "text_deep_grad: bad arguments (C=%d T=%d P=%d prefix_classes=%d d=%d)", C, T, P, prefix_classes, d);
+    const int waves = prefix_classes * P * ((d / 4 + 63) / 64);
+    hipLaunchKernelGGL(text_prefix_grad_kernel<true>, dim3((waves + 3) / 4), dim3(256), 0, s, (const float*)dx, scale, grad, C, T, P, prefix_classes, d, dxh);
     GRIP_CHECK_HIP(hipGetLastError());
     return GRIP_OK;
 }

@@ -201,6 +201,7 @@ struct Workspace {  // carve of the caller's buffer for one (batch, n_prefix, tr
     int hilo = 0;              // ... and whether this forward does
     const float* deep = nullptr;   // deep visual prompts [n_deep, P, d] f32 (grip_vit_forward_deep): rows 1 .. P of block l's input := deep[l - 1], 1 <= l <= n_deep
     int n_deep = 0;
+    int deep_classes = 1;          // text tower (grip_text_forward_deep): deep is [n_deep, deep_classes, P, d], one context per class when deep_classes == batch
     // train-mode saves, one per layer (x_in has layers+1 entries)
     std::vector<resid_t*> x_in, x_mid;
     std::vector<half_t*> qkv_l, att_l, hpre_l;
@@ -250,7 +251,7 @@ struct grip_tower {
         const int32_t* eot = nullptr;
         int prefix_classes = 0;
         bool per_image = false;    // vision: the forward ran with GRIP_FWD_PER_IMAGE_PREFIX (prefix and its gradient are [batch, n_prefix, width])
-        int n_deep = 0;            // vision: deep visual prompts of the forward (grip_vit_forward_deep): its backward is grip_vit_backward_deep
+        int n_deep = 0;            // deep prompts of the forward (grip_vit_forward_deep / grip_text_forward_deep): its backward is grip_vit_backward_deep / grip_text_backward_deep
         uint64_t generation = 0;
         bool consumed = false;     // its backward has run (the backward works in place on the saved activations: one per forward)
     };
@@ -488,9 +489,14 @@ static int run_blocks(grip_tower* t, Workspace& w, resid_t* x0, int causal, cons
     for (int l = 0; l < t->D.layers; ++l) {
         const LayerW& lw = t->L.layer[(size_t)l];
         const bool last = l + 1 == t->D.layers;
-        if (l >= 1 && l <= w.n_deep)      // deep prompts: the block's input rows 1 .. P := deep[l - 1] before anything reads x (train: x_in[l], what the backward differentiates)
-            RUN(launch_vit_deep_insert(w.deep + (size_t)(l - 1) * w.P * d, x, f, hilo ? w.x_lo : nullptr, parts_in ? w.stat_part : nullptr,
-                                       (fold && !parts_in) ? w.rowstat : nullptr, w.batch, w.S, w.P, (int)w.M, d, s));
+        if (l >= 1 && l <= w.n_deep) {    // deep prompts: the block's input rows 1 .. P := deep[l - 1] before anything reads x (train: x_in[l], what the backward differentiates)
+            if (t->D.kind == 0)
+                RUN(launch_vit_deep_insert(w.deep + (size_t)(l - 1) * w.P * d, x, f, hilo ? w.x_lo : nullptr, parts_in ? w.stat_part : nullptr,
+                                           (fold && !parts_in) ? w.rowstat : nullptr, w.batch, w.S, w.P, (int)w.M, d, s));
+            else      // text tower: either row layout, one context for every class or one per class
+                RUN(launch_text_deep_insert(w.deep + (size_t)(l - 1) * w.deep_classes * w.P * d, w.deep_classes, x, f, parts_in ? w.stat_part : nullptr,
+                                            (fold && !parts_in) ? w.rowstat : nullptr, w.batch, w.S, w.P, w.Ps, (int)w.M, d, s));
+        }
         if (last && rows_only) {
             // K and V of every row (columns d .. 3d of the packed projection); Q only for the rows that are read
             GemmArgs a{};
@@ -709,11 +715,15 @@ extern "C" int grip_vit_forward(grip_tower* t, const void* images, int images_f1
     return grip_vit_forward_deep(t, images, images_f16, prefix, n_prefix, nullptr, 0, batch, out_emb, workspace, workspace_bytes, flags, generation, stream);
 }
 
-extern "C" int grip_text_forward(grip_tower* t, const int32_t* token_ids, const int32_t* eot_index, const float* prefix,
-                                 int n_prefix, int prefix_classes, int n_class, int seq_len, float* out_emb,
-                                 void* workspace, size_t workspace_bytes, int flags, uint64_t* generation, void* stream) {
+extern "C" int grip_text_forward_deep(grip_tower* t, const int32_t* token_ids, const int32_t* eot_index, const float* prefix,
+                                      int n_prefix, int prefix_classes, const float* deep, int n_deep, int n_class, int seq_len, float* out_emb,
+                                      void* workspace, size_t workspace_bytes, int flags, uint64_t* generation, void* stream) {
     try {
-        GRIP_REQUIRE(t && t->D.kind == 1, "text_forward: not a text tower");
+        GRIP_REQUIRE(t && t->D.kind == 1, "text_forward: not a text tower%s", n_deep ? " (the vision tower's deep prompts go through grip_vit_forward_deep)" : "");
+        GRIP_REQUIRE(n_deep >= 0 && n_deep <= t->D.layers - 1, "text_forward_deep: n_deep = %d out of range: deep prompts replace the context rows entering blocks 1 .. n_deep, "
+                     "0 <= n_deep <= layers - 1 = %d", n_deep, t->D.layers - 1);
+        GRIP_REQUIRE(n_deep == 0 || n_prefix > 0, "text_forward_deep: deep prompts replace the rows of the shallow context: n_prefix must be positive (n_deep = %d)", n_deep);
+        GRIP_REQUIRE(n_deep == 0 || deep, "text_forward_deep: null deep prompt pointer (n_deep = %d)", n_deep);
         GRIP_REQUIRE(token_ids && eot_index && out_emb && (n_prefix == 0 || prefix), "text_forward: null pointer");
         GRIP_REQUIRE(!(flags & GRIP_FWD_PER_IMAGE_PREFIX), "text_forward: GRIP_FWD_PER_IMAGE_PREFIX is a vision-tower flag (one context per class: prefix_classes = n_class)");
         GRIP_REQUIRE(n_prefix == 0 || prefix_classes == 1 || prefix_classes == n_class, "text_forward: prefix_classes must be 1 or n_class");
@@ -723,6 +733,9 @@ extern "C" int grip_text_forward(grip_tower* t, const int32_t* token_ids, const 
         const int shared = (flags & GRIP_FWD_SHARED_PREFIX) && n_prefix > 0 && prefix_classes == 1 && !t->f32;
         Workspace w;
         RUN(check_ws(t, n_class, n_prefix, train, workspace, workspace_bytes, w, seq_len, shared));
+        w.deep = n_deep ? deep : nullptr;
+        w.n_deep = n_deep;
+        w.deep_classes = n_deep ? prefix_classes : 1;
         hipStream_t s = (hipStream_t)stream;
         const grip_dims& D = t->D;
         const int d = D.width, f = t->f32;
@@ -737,9 +750,16 @@ extern "C" int grip_text_forward(grip_tower* t, const int32_t* token_ids, const 
         GemmArgs a{};
         a.f32 = f; a.A = w.cls16; a.W = t->wop(t->L.projT); a.M = n_class; a.N = D.embed_dim; a.K = d; a.out = out_emb; a.ldc = D.embed_dim;
         RUN(launch_gemm(EPI_F32, a, s));
-        note_forward(t, workspace, train, w, eot_index, prefix_classes, generation);
+        note_forward(t, workspace, train, w, eot_index, prefix_classes, generation, false, n_deep);
         return GRIP_OK;
     } catch (...) { grip_set_error("text_forward: exception"); return GRIP_ERR_ARG; }
+}
+
+extern "C" int grip_text_forward(grip_tower* t, const int32_t* token_ids, const int32_t* eot_index, const float* prefix,
+                                 int n_prefix, int prefix_classes, int n_class, int seq_len, float* out_emb,
+                                 void* workspace, size_t workspace_bytes, int flags, uint64_t* generation, void* stream) {
+    return grip_text_forward_deep(t, token_ids, eot_index, prefix, n_prefix, prefix_classes, nullptr, 0, n_class, seq_len, out_emb, workspace, workspace_bytes, flags,
+                                  generation, stream);
 }
 
 // ---------------------------------------------------------------------------------------------- test hooks
@@ -841,6 +861,8 @@ extern "C" int grip_debug_layernorm(const float* x, const float* gamma, const fl
 // (loss-scaled) gradient w.r.t. the final residual stream, leaves with dx = gradient w.r.t. x0.
 // grad_deep (deep visual prompts, w.n_deep > 0): [n_deep, P, d]; before block l's backward, dx / dxh hold the gradient of x_in[l + 1], whose rows
 // 1 .. P the forward overwrote with deep[l] when l + 1 <= n_deep: their batch sum is grad_deep[l], and they are zeroed (nothing flows below).
+// Text tower: [n_deep, deep_classes, P, d], the class sum for one shared context, each class's own rows otherwise.  In the shared-prefix layout the
+// classes' shares have already met in the shared rows (attention_bwd's kv_part reduction), so the slice runs as one sequence.
 static int run_blocks_backward(grip_tower* t, Workspace& w, int causal, const int32_t* read_rows, hipStream_t s, float* grad_deep = nullptr) {
     const int d = t->D.width, H = t->D.heads;
     const half_t* W = t->w16;
@@ -848,8 +870,12 @@ static int run_blocks_backward(grip_tower* t, Workspace& w, int causal, const in
     const int64_t part = (int64_t)w.Mp * d;       // floats between split-K partial buffers in w.dln
     for (int l = t->D.layers - 1; l >= 0; --l) {
         const LayerW& lw = t->L.layer[(size_t)l];
-        if (grad_deep && l + 1 <= w.n_deep)
-            RUN(launch_vit_deep_grad(w.dx, w.dxh, w.scale, grad_deep + (size_t)l * w.P * d, w.batch, w.S, w.P, d, s));
+        if (grad_deep && l + 1 <= w.n_deep) {
+            if (t->D.kind == 0)
+                RUN(launch_vit_deep_grad(w.dx, w.dxh, w.scale, grad_deep + (size_t)l * w.P * d, w.batch, w.S, w.P, d, s));
+            else
+                RUN(launch_text_deep_grad(w.dx, w.dxh, w.scale, grad_deep + (size_t)l * w.deep_classes * w.P * d, w.Ps ? 1 : w.batch, w.S, w.P, w.deep_classes, d, s));
+        }
         if (l + 1 == t->D.layers && w.rows_last) {
             // the last block ran for the read rows only (run_blocks): enters with drow / drow_h = the gradient of those stream rows
             const int64_t Bp = round_up64(w.batch, 256);
@@ -991,23 +1017,48 @@ extern "C" int grip_vit_backward_deep(grip_tower* t, const float* grad_emb, cons
     } catch (...) { grip_set_error("vit_backward_deep: exception"); return GRIP_ERR_ARG; }
 }
 
+// (who: the entry point's name for the messages; grad_deep is only read when the forward ran with deep prompts)
+static int text_backward(const char* who, grip_tower* t, const float* grad_emb, float* grad_prefix, float* grad_deep,
+                         void* workspace, size_t workspace_bytes, uint64_t generation, void* stream) {
+    GRIP_REQUIRE(t && t->D.kind == 1 && grad_emb && grad_prefix, "%s: bad arguments", who);
+    grip_tower::TrainState st;
+    RUN(check_bwd(t, workspace, workspace_bytes, generation, st));
+    Workspace& w = st.w;
+    GRIP_REQUIRE(w.P > 0, "%s: forward had no prompt tokens", who);
+    hipStream_t s = (hipStream_t)stream;
+    RUN(backward_head_of_tower(t, w, grad_emb, st.eot, s));
+    RUN(run_blocks_backward(t, w, 1, st.eot, s, st.n_deep ? grad_deep : nullptr));
+    if (w.Ps)   // shared-prefix layout: every class's share already met in the shared rows (rows 1 .. P)
+        RUN(launch_text_prefix_grad(w.dx, w.scale, grad_prefix, 1, w.S, w.P, 1, t->D.width, s));
+    else
+        RUN(launch_text_prefix_grad(w.dx, w.scale, grad_prefix, w.batch, w.S, w.P, st.prefix_classes, t->D.width, s));
+    return GRIP_OK;
+}
+
 extern "C" int grip_text_backward_prefix(grip_tower* t, const float* grad_emb, float* grad_prefix,
                                          void* workspace, size_t workspace_bytes, uint64_t generation, void* stream) {
     try {
-        GRIP_REQUIRE(t && t->D.kind == 1 && grad_emb && grad_prefix, "text_backward_prefix: bad arguments");
-        grip_tower::TrainState st;
-        RUN(check_bwd(t, workspace, workspace_bytes, generation, st));
-        Workspace& w = st.w;
-        GRIP_REQUIRE(w.P > 0, "text_backward_prefix: forward had no prompt tokens");
-        hipStream_t s = (hipStream_t)stream;
-        RUN(backward_head_of_tower(t, w, grad_emb, st.eot, s));
-        RUN(run_blocks_backward(t, w, 1, st.eot, s));
-        if (w.Ps)   // shared-prefix layout: every class's share already met in the shared rows (rows 1 .. P)
-            RUN(launch_text_prefix_grad(w.dx, w.scale, grad_prefix, 1, w.S, w.P, 1, t->D.width, s));
-        else
-            RUN(launch_text_prefix_grad(w.dx, w.scale, grad_prefix, w.batch, w.S, w.P, st.prefix_classes, t->D.width, s));
-        return GRIP_OK;
+        if (t && t->D.kind == 1) {
+            auto it = t->pending.find(workspace);
+            if (it != t->pending.end() && it->second.n_deep > 0 && !it->second.consumed) {
+                grip_set_error("text_backward_prefix: the forward on this workspace ran with %d deep prompts: its backward is grip_text_backward_deep", it->second.n_deep);
+                return GRIP_ERR_STATE;
+            }
+        }
+        return text_backward("text_backward_prefix", t, grad_emb, grad_prefix, nullptr, workspace, workspace_bytes, generation, stream);
     } catch (...) { grip_set_error("text_backward_prefix: exception"); return GRIP_ERR_ARG; }
+}
+
+extern "C" int grip_text_backward_deep(grip_tower* t, const float* grad_emb, float* grad_prefix, float* grad_deep,
+                                       void* workspace, size_t workspace_bytes, uint64_t generation, void* stream) {
+    try {
+        if (t && t->D.kind == 1) {
+            auto it = t->pending.find(workspace);
+            GRIP_REQUIRE(it == t->pending.end() || it->second.n_deep == 0 || grad_deep, "text_backward_deep: null grad_deep (the forward ran with %d deep prompts)",
+                         it == t->pending.end() ? 0 : it->second.n_deep);
+        }
+        return text_backward("text_backward_deep", t, grad_emb, grad_prefix, grad_deep, workspace, workspace_bytes, generation, stream);
+    } catch (...) { grip_set_error("text_backward_deep: exception"); return GRIP_ERR_ARG; }
 }
 
 extern "C" int grip_debug_attention_bwd(const void* qkv, const void* o, const void* d_out, void* dqkv, int B, int S, int H, int causal, void* stream) {

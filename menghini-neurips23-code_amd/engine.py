@@ -309,7 +309,18 @@ class Tower:
     # read, so later positions cannot influence any output (exact; the reference encodes all 77).
     truncate_text_at_eot = True
 
-    def text_forward(self, token_ids, prefix=None, train=False, seq_len=None, pos_emb=True):
+    def text_deep(self, deep, pc, P):
+        """Deep text prompts as the native call takes them: (deep f32 contiguous [D, pc, P, d] or None, D).  deep[l - 1] replaces the context rows of the
+        stream entering block l, 1 <= l <= D <= layers - 1 (grip_text_forward_deep, include/grip_amd.h).  A shared context (pc == 1) takes [D, P, d] or
+        [D, 1, P, d], a class-specific one [D, C, P, d]."""
+        if deep is None:
+            return None, 0
+        check_text_deep_prompts(deep, pc, P, self.width, self.dims.layers)
+        return deep.reshape(deep.shape[0], pc, P, self.width).contiguous().float(), deep.shape[0]
+
+    def text_forward(self, token_ids, prefix=None, train=False, seq_len=None, pos_emb=True, deep=None):
+        """CustomTextEncoder.forward: prefix None or [pc, P, d] (pc = 1: one context for every class, or one per class); deep None or the deep
+        prompts of that context (text_deep)."""
         if not self._finalized:
             self.finalize()
         assert self.kind == 1
@@ -329,6 +340,7 @@ class Tower:
         if prefix is not None:
             pc, P = prefix.shape[0], prefix.shape[1]
             prefix = prefix.contiguous().float()
+        deep, D = self.text_deep(deep, pc, P)
         flags = (native.FWD_TRAIN if train else 0) | (0 if pos_emb else native.FWD_NO_POS_EMB)
         if P and pc == 1 and not self.exact and self.share_text_prefix and self._shares_prefix(token_ids, ids, eot, P):
             flags |= native.FWD_SHARED_PREFIX
@@ -337,9 +349,14 @@ class Tower:
         ws = self.workspace(C, P, train, seq_len)
         p, n = self._aligned(ws)
         gen = c_uint64(0)
-        native.check(self.lib.grip_text_forward(self.handle, _ptr(ids), _ptr(eot), _ptr(prefix), P, pc, C, seq_len, _ptr(out), p, n,
-                                                flags, byref(gen), _stream()))
+        if D:
+            native.check(self.lib.grip_text_forward_deep(self.handle, _ptr(ids), _ptr(eot), _ptr(prefix), P, pc, _ptr(deep), D, C, seq_len, _ptr(out), p, n,
+                                                         flags, byref(gen), _stream()))
+        else:
+            native.check(self.lib.grip_text_forward(self.handle, _ptr(ids), _ptr(eot), _ptr(prefix), P, pc, C, seq_len, _ptr(out), p, n,
+                                                    flags, byref(gen), _stream()))
         ws.generation = gen.value
+        ws.n_deep = D         # the backward then returns grad_deep [D, pc, P, d] as well
         return out, ws, (ids, eot, seq_len)
 
     # One shared context (CoOp / UPT text side): positions 0 .. P hold the same tokens for every class and the mask is causal, so
@@ -359,9 +376,16 @@ class Tower:
         return ok
 
     def text_backward(self, grad_emb, prefix_shape, ws, generation=0):
+        """Context gradient [pc, P, d] of the train-mode forward on `ws` (summed over the classes when pc == 1).  After a forward with deep prompts:
+        (context gradient, deep-prompt gradient [D, pc, P, d])."""
         grad_emb = grad_emb.contiguous().float()
         g = torch.empty(prefix_shape, dtype=torch.float32, device=self.device)
         p, n = self._aligned(ws)
+        D = getattr(ws, "n_deep", 0)
+        if D:
+            gd = torch.empty((D,) + tuple(prefix_shape), dtype=torch.float32, device=self.device)
+            native.check(self.lib.grip_text_backward_deep(self.handle, _ptr(grad_emb), _ptr(g), _ptr(gd), p, n, generation, _stream()))
+            return g, gd
         native.check(self.lib.grip_text_backward_prefix(self.handle, _ptr(grad_emb), _ptr(g), p, n, generation, _stream()))
         return g
 
@@ -372,6 +396,18 @@ def check_deep_prompts(deep, P, width, layers):
     if deep.dim() != 3 or deep.shape[1] != P or deep.shape[2] != width or not 1 <= deep.shape[0] <= layers - 1:
         raise native.GripError(f"deep visual prompts of shape {tuple(deep.shape)}: expected [D, {P}, {width}] with 1 <= D <= {layers - 1} "
                                f"(the shallow prompt's P = {P} and width; one prompt per block after the first)")
+
+
+def check_text_deep_prompts(deep, pc, P, width, layers):
+    """Deep text prompts must be [D, P, width] or [D, 1, P, width] for one shared context (pc == 1), [D, C, P, width] for a class-specific one (pc == C),
+    with 1 <= D <= layers - 1 and the shallow context's token count P (they replace its rows).  Raises GripError otherwise."""
+    ok = torch.is_tensor(deep) and deep.dim() in (3, 4) and P > 0 and 1 <= deep.shape[0] <= layers - 1 and (
+        tuple(deep.shape[1:]) == (pc, P, width) or (pc == 1 and tuple(deep.shape[1:]) == (P, width)))
+    if not ok:
+        want = f"[D, {P}, {width}] (or [D, 1, {P}, {width}])" if pc == 1 else f"[D, {pc}, {P}, {width}]"
+        raise native.GripError(f"deep text prompts of shape {tuple(deep.shape) if torch.is_tensor(deep) else type(deep).__name__}: expected {want} with "
+                               f"1 <= D <= {layers - 1} (the shallow context's {'one shared set' if pc == 1 else 'C = ' + str(pc) + ' per-class sets'} of "
+                               f"P = {P} tokens and width; one prompt per block after the first)")
 
 
 def is_per_image_prefix(prefix):
@@ -422,28 +458,33 @@ class VitPrefixFn(torch.autograd.Function):
 
 
 class TextPrefixFn(torch.autograd.Function):
-    """CustomTextEncoder.forward with autograd to the textual prompt only."""
+    """CustomTextEncoder.forward with autograd to the textual prompt only -- and, when given, to its deep prompts (the gradient in deep's own
+    shape and dtype)."""
 
     @staticmethod
-    def forward(ctx, tower, token_ids, prefix, pos_emb=True):
-        need = ctx.needs_input_grad[2]
+    def forward(ctx, tower, token_ids, prefix, pos_emb=True, deep=None):
+        need = ctx.needs_input_grad[2] or (deep is not None and ctx.needs_input_grad[4])
         if need and tower.exact:
             raise native.GripError("exact (f32) towers are inference-only: prompt gradients need a default-precision tower")
         cached = getattr(token_ids, "_grip_seq_len", None)
-        out, ws, keep = tower.text_forward(token_ids, prefix.detach(), train=need, seq_len=cached, pos_emb=pos_emb)
+        out, ws, keep = tower.text_forward(token_ids, prefix.detach(), train=need, seq_len=cached, pos_emb=pos_emb, deep=None if deep is None else deep.detach())
         token_ids._grip_seq_len = keep[2]
         ctx.tower, ctx.ws, ctx.generation = tower, ws, ws.generation
         if need:
             tower.hold(ws, ctx)
         ctx.keep = keep   # the native handle remembers the EOT-index pointer until backward
         ctx.pshape, ctx.pdtype = prefix.shape, prefix.dtype
+        ctx.dshape, ctx.ddtype = (None, None) if deep is None else (deep.shape, deep.dtype)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         g = ctx.tower.text_backward(grad_out, tuple(ctx.pshape), ctx.ws, ctx.generation)
         ctx.tower.release(ctx.ws)
-        return None, None, g.to(ctx.pdtype), None
+        if ctx.dshape is None:
+            return None, None, g.to(ctx.pdtype), None
+        g, gd = g
+        return None, None, g.to(ctx.pdtype), None, gd.reshape(ctx.dshape).to(ctx.ddtype)
 
 
 def vit_prefix_forward(tower, images, prefix, pos_emb=True, deep=None):
@@ -461,13 +502,17 @@ def vit_prefix_forward(tower, images, prefix, pos_emb=True, deep=None):
     return tower.vit_forward(images, prefix.detach(), train=False, pos_emb=pos_emb, deep=deep.detach())[0]
 
 
-def text_prefix_forward(tower, token_ids, prefix, pos_emb=True):
+def text_prefix_forward(tower, token_ids, prefix, pos_emb=True, deep=None):
     """CustomTextEncoder.forward on the native tower; see vit_prefix_forward.  pos_emb=False is the reference's enable_pos_emb=False
-    branch (models/clip_encoders.py:70-74): the positional embedding is not added (the positions' gradient path is untouched: it is additive)."""
-    if torch.is_grad_enabled() and prefix.requires_grad:
-        return TextPrefixFn.apply(tower, token_ids, prefix, pos_emb)
+    branch (models/clip_encoders.py:70-74): the positional embedding is not added (the positions' gradient path is untouched: it is additive).
+    deep: None or the context's deep prompts ([D, P, d] / [D, 1, P, d] shared, [D, C, P, d] per class; Tower.text_deep); differentiable as well."""
+    if deep is None:
+        if torch.is_grad_enabled() and prefix.requires_grad:
+            return TextPrefixFn.apply(tower, token_ids, prefix, pos_emb)
+    elif torch.is_grad_enabled() and (prefix.requires_grad or deep.requires_grad):
+        return TextPrefixFn.apply(tower, token_ids, prefix, pos_emb, deep)
     cached = getattr(token_ids, "_grip_seq_len", None)
-    out, _, keep = tower.text_forward(token_ids, prefix.detach(), train=False, seq_len=cached, pos_emb=pos_emb)
+    out, _, keep = tower.text_forward(token_ids, prefix.detach(), train=False, seq_len=cached, pos_emb=pos_emb, deep=None if deep is None else deep.detach())
     token_ids._grip_seq_len = keep[2]
     return out
 

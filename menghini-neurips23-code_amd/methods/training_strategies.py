@@ -71,6 +71,8 @@ class TrainingStrategy:
             return torch.randn(*shape, generator=g) * std + mean
         if self.modality == "text":
             self.initial_prefix = init(1, int(c.PREFIX_SIZE), d.transformer_width)
+            # COOP_DEEP: deep contexts for blocks 1 .. layers - 1, drawn after the shallow context (which stays bit-identical with and without them)
+            self.initial_deep_prefix = init(d.transformer_layers - 1, int(c.PREFIX_SIZE), d.transformer_width) if self.coop_deep() else None
         elif self.modality == "image":
             self.initial_prefix = init(int(c.PREFIX_SIZE), d.vision_width)
             # VPT_DEEP: deep prompts for blocks 1 .. layers - 1, drawn after the shallow prompt (which stays bit-identical with and without them)
@@ -86,6 +88,11 @@ class TrainingStrategy:
         reference does (its UPT computes vpt_embeddings_deep and discards it); they have UPT_DEEP."""
         return self.modality == "image" and bool(getattr(self.config, "VPT_DEEP", False))
 
+    def coop_deep(self):
+        """Deep text prompts (deep CoOp) for the textual strategies: config COOP_DEEP, default False.  The visual strategies have no trainable text
+        side and the multimodal ones keep UPT's single mixed context: both ignore it."""
+        return self.modality == "text" and bool(getattr(self.config, "COOP_DEEP", False))
+
     def upt_deep(self):
         """Deep UPT for the multimodal strategies: config UPT_DEEP, default False.  UPTModel(mix_deep=True) mixes vpt_embeddings_deep with the
         prompts and feeds its outputs to the image tower as deep prompts."""
@@ -95,7 +102,9 @@ class TrainingStrategy:
         c, dev = self.config, self.device
         classes = classes if classes is not None else self.classes
         if self.modality == "text":
-            self.model = TextPrefixModel(self.initial_prefix.clone().to(dev), self.text_encoder, classes, device=dev)
+            deep = getattr(self, "initial_deep_prefix", None)
+            self.model = TextPrefixModel(self.initial_prefix.clone().to(dev), self.text_encoder, classes, device=dev,
+                                         deep_prefix=None if deep is None else deep.clone().to(dev))
         elif self.modality == "image":
             deep = getattr(self, "initial_deep_prefix", None)
             self.model = ImagePrefixModel(self.initial_prefix.clone().to(dev), self.image_encoder, device=dev,
@@ -127,7 +136,7 @@ class TrainingStrategy:
 
     def prompt_snapshot(self):
         m = self.unwrap_model()
-        if self.modality == "image" and getattr(m, "deep_prefix", None) is not None:
+        if self.modality in ("text", "image") and getattr(m, "deep_prefix", None) is not None:      # VPT-Deep / deep CoOp
             return [m.prefix.detach().cpu().numpy(), m.deep_prefix.detach().cpu().numpy()]
         if self.modality in ("text", "image"):
             return [m.prefix.detach().cpu().numpy()]
@@ -388,7 +397,8 @@ class TrainingStrategy:
         from ..engine import text_prefix_forward
         if self.modality == "text":
             ids = self.text_encoder._token_ids(self.model.prefix.shape[1], classes)
-            return text_prefix_forward(clip_model.text_tower, ids, self.model.prefix.detach()), None
+            deep = getattr(self.model, "deep_prefix", None)      # deep CoOp: the twin's text tower reads the same deep prompts
+            return text_prefix_forward(clip_model.text_tower, ids, self.model.prefix.detach(), deep=None if deep is None else deep.detach()), None
         if self.modality == "image":
             return clip_model.encode_text(clip.tokenize(self.text_prompts(classes)).to(self.device)), self.model.prefix.detach()
         coop_embs, vpt_embs = self.model.mix()[:2]

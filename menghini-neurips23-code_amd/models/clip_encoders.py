@@ -52,9 +52,13 @@ class CustomTextEncoder(nn.Module):
             self._tok_cache[key] = ids
         return ids
 
-    def forward(self, class_embeddings, classes, enable_pos_emb=True):
+    def forward(self, class_embeddings, classes, enable_pos_emb=True, deep_prompts=None):
+        """deep_prompts: None or the context's deep prompts (deep CoOp): [D, P, d] (or [D, 1, P, d]) with a shared context, [D, C, P, d] with one
+        context per class, 1 <= D <= layers - 1.  Before block l (1 <= l <= D) positions 1 .. P of every class's stream are replaced by
+        deep_prompts[l - 1], no LayerNorm and no positional embedding -- the text-tower mirror of CustomVisionTransformer's deep_prompts.
+        Differentiable, as class_embeddings is."""
         token_ids = self._token_ids(class_embeddings.size()[1], classes)
-        return text_prefix_forward(self.clip_model.text_tower, token_ids, class_embeddings, pos_emb=bool(enable_pos_emb))   # :70-74
+        return text_prefix_forward(self.clip_model.text_tower, token_ids, class_embeddings, pos_emb=bool(enable_pos_emb), deep=deep_prompts)   # :70-74
 
 
 class ImageEncoder(nn.Module):

@@ -31,16 +31,20 @@ class _ModuleShim:
 
 
 class TextPrefixModel(_ModuleShim, nn.Module):
-    def __init__(self, initial_prefix, text_encoder, classes, temperature=0.07, device="cpu"):
+    def __init__(self, initial_prefix, text_encoder, classes, temperature=0.07, device="cpu", deep_prefix=None):
         super().__init__()
         self.device = device
         self.initialized_prefix = initial_prefix
         self.classes = classes
         self.prefix = nn.Parameter(initial_prefix)
         self.text_encoder = text_encoder
+        # deep CoOp: [D, P, d] prompts replacing the context rows entering blocks 1 .. D (CustomTextEncoder.forward(deep_prompts=))
+        self.deep_prefix = nn.Parameter(deep_prefix) if deep_prefix is not None else None
 
     def forward(self, classes):
-        return self.text_encoder(self.prefix, classes)     # un-normalised, as reference :31-36
+        if self.deep_prefix is None:
+            return self.text_encoder(self.prefix, classes)     # un-normalised, as reference :31-36
+        return self.text_encoder(self.prefix, classes, deep_prompts=self.deep_prefix)
 
 
 class ImagePrefixModel(_ModuleShim, nn.Module):

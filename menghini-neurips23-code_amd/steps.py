@@ -47,6 +47,13 @@ def _finish(loss, params, optimizer, logits=None):
     return loss.detach() if logits is None else (loss.detach(), logits.detach())
 
 
+def _coop_params(model):
+    """The textual model's trainable tensors: the context and, with deep CoOp (model.deep_prefix [D, P, d]), its deep prompts -- their gradient is
+    all-reduced with the context's."""
+    deep = getattr(model, "deep_prefix", None)
+    return [model.prefix] if deep is None else [model.prefix, deep]
+
+
 def coop_step(model, clip_model, images, labels, row_weight, optimizer, image_features=None, return_logits=False):
     """Textual prompt step: text tower forward+backward over all class prompts, frozen image tower
     forward only (or cached features)."""
@@ -64,7 +71,7 @@ def coop_step(model, clip_model, images, labels, row_weight, optimizer, image_fe
         image_features.record_stream(torch.cuda.current_stream())
     logits = CosineHeadFn.apply(image_features, text_features, clip_model.logit_scale.exp().item())
     loss = WeightedCEFn.apply(logits, labels, row_weight)
-    return _finish(loss, [model.prefix], optimizer, logits if return_logits else None)
+    return _finish(loss, _coop_params(model), optimizer, logits if return_logits else None)
 
 
 def vpt_step(model, text_features, logit_scale, images, labels, row_weight, optimizer, return_logits=False):
@@ -178,7 +185,8 @@ class GraphedStep:
 
 
 class GraphedCoopStep(GraphedStep):
-    """coop_step (textual prompt: text tower forward + backward, frozen image tower on a side stream) replayed from a HIP graph."""
+    """coop_step (textual prompt: text tower forward + backward, frozen image tower on a side stream) replayed from a HIP graph.  A model with deep
+    prompts (deep CoOp, model.deep_prefix) has them captured as one more static parameter."""
 
     def __init__(self, model, clip_model, optimizer):
         super().__init__(optimizer)
@@ -186,7 +194,7 @@ class GraphedCoopStep(GraphedStep):
         self.scale = clip_model.logit_scale.exp().item()
 
     def params(self):
-        return [self.model.prefix]
+        return _coop_params(self.model)
 
     def shape_key(self, images):
         return (tuple(images.shape), images.dtype, tuple(self.model.classes))
@@ -214,7 +222,7 @@ class GraphedCoopFeatureStep(GraphedStep):
         self.scale = clip_model.logit_scale.exp().item()
 
     def params(self):
-        return [self.model.prefix]
+        return _coop_params(self.model)
 
     def shape_key(self, feats):
         return (tuple(feats.shape), feats.dtype, tuple(self.model.classes))
