@@ -11,7 +11,7 @@ extern "C" {
 
 /* out[M,N] = epilogue(A[M,K] W[N,K]^T).  epi: 0 f32 out, 1 +bias -> f16, 2 +bias, QuickGELU -> f16 (out2 = pre-activation or
  * NULL), 3 +bias +resid(f16) -> f16, 4 f16, 5 * QuickGELU'(aux) -> f16, 6 f32 * scalar.  A has m_pad >= M rows allocated.
- * variant: 0 = launcher's choice, 1..6 = a specific tile kernel (csrc/gemm.hip); 7 = the exact-mode kernel (csrc/gemm_f32.hip):
+ * variant: 0 = launcher's choice, 1..6 and 8 = a specific tile kernel (csrc/gemm_plan.cpp); 7 = the exact-mode kernel (csrc/gemm_f32.hip):
  * A, W, resid and every output are f32 (epi 0..3 and 6 only). */
 int grip_debug_gemm(int epi, const void* A, const void* W, int M, int N, int K, const float* bias, const void* resid,
                     const void* aux, void* out, void* out2, float scalar, int m_pad, int variant, void* stream);
@@ -33,6 +33,13 @@ int grip_debug_coop_split(int M, int N, int K);
  * partial p = A[:, Kp] W[:, Kp]^T over the p-th K range.  ksplit = 0: the launcher's own choice; *ksplit_used receives the factor. */
 int grip_debug_gemm_splitk(const void* A, const void* W, int M, int N, int K, float* out, int ksplit, int64_t split_stride, int* ksplit_used,
                            int m_pad, int variant, void* stream);
+/* Which kernel a GEMM launch would get (csrc/gemm_plan.cpp), without launching anything: works on a machine without a GPU.  The inputs are what the
+ * launcher reads of GemmArgs: the integers, `present` = which optional buffers are set (bit 0 stat_part, 1 stat_in, 2 rowstat, 3 out2, 4 coop_scratch and
+ * coop_counter), and n_cu = the CUs the launch may use.  The GRIP_GEMM_* knobs of the process apply.  text receives one line,
+ *   "gemm_ringw_kernel<3, 4, 1> grid 56x4 block 512 lds 81920 static_lds 0 tiles 14x4 colgroup 0 rot 2 finalize 0 variant 4"
+ * (the kernel as a profiler names it; lds = dynamic bytes of the launch, static_lds = what the kernel itself declares), or the message of a refused shape, which is also the return code's grip_last_error(). */
+int grip_debug_gemm_plan(int epi, int M, int N, int K, int ldc, int64_t m_pad, int variant, int ksplit, int f32, int rot_rows, int present,
+                         int stat_parts, int64_t split_stride, int n_cu, char* text, int text_len);
 /* Wg = f16(gamma o W) [N, K], colsum[n] = sum_k Wg[n][k], bias_out = bias + W beta; then, if stat_part != NULL,
  * rowstat [M, 2] = (mean, rstd) from the [M, parts, 2] partial sums over rows of width d. */
 int grip_debug_ln_fold(const void* W, const float* gamma, const float* beta, const float* bias, void* Wg, float* colsum, float* bias_out,
@@ -61,7 +68,7 @@ int grip_debug_layernorm(const float* x, const float* gamma, const float* beta, 
 
 /* GEMM launch profiler: while enabled, every 4th GEMM launch is bracketed by HIP events on its stream. */
 int grip_profile_enable(int on);
-/* Per slot (variant * 8 + epilogue id) in [0, n): launches sampled, their total milliseconds and total 2*M*N*K. */
+/* Per slot (variant * 16 + epilogue id) in [0, n): launches sampled, their total milliseconds and total 2*M*N*K. */
 int grip_profile_collect(int n, int64_t* launches, double* total_ms, double* total_flops);
 
 #ifdef __cplusplus

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "host_common.h"
+#include "gemm_plan.h"
 
 typedef _Float16 half_t;
 typedef half_t half8 __attribute__((ext_vector_type(8)));
@@ -34,25 +35,7 @@ int grip_cu_budget();      // grip_set_cu_budget (tower.hip): CUs the persistent
 
 static inline int64_t round_up64(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
-// ---------------------------------------------------------------------------------------------
-// GEMM: C[M,N] = epilogue(A[M,K] * W[N,K]^T).  A and W are f16, K-contiguous; accumulate f32.
-enum GemmEpi {
-    EPI_F32 = 0,             // out_f32 = acc
-    EPI_BIAS_F16 = 1,        // out_f16 = acc + bias
-    EPI_BIAS_GELU_F16 = 2,   // out_f16 = quickgelu(acc + bias); if out2 != null, out2_f16 = acc + bias (pre-activation)
-    EPI_BIAS_RESID = 3,      // out_resid = resid + acc + bias   (residual stream, resid_t)
-    EPI_F16 = 4,             // out_f16 = acc
-    EPI_GELUGRAD_F16 = 5,    // out_f16 = acc * quickgelu'(aux_f16)       (backward of c_fc activation)
-    EPI_F32_SCALE = 6,       // out_f32 = acc * scalar
-    // LayerNorm folded into the GEMM that consumes it (A = the RAW residual stream, W = gamma-scaled weights W' = f16(gamma o W)):
-    //   LN(x) W^T + b  =  rstd_r * (x W'^T - mean_r * colsum(W')) + (W beta + b)
-    // rowstat[r] = (mean_r, rstd_r), colsum[n] = sum_k W'[n][k], bias[n] = (W beta + b)[n]
-    EPI_LNFOLD_F16 = 7,      // out_f16 = rstd * (acc - mean * colsum) + bias
-    EPI_LNFOLD_GELU_F16 = 8, // out_f16 = quickgelu(that); if out2 != null, out2_f16 = that (pre-activation)
-    EPI_BIAS_RESID_STATS = 9,// EPI_BIAS_RESID + the row statistics (GemmArgs.stat_part); chosen by the launcher, never passed in by callers
-    EPI_COUNT = 10
-};
-
+// (enum GemmEpi, the GEMM epilogues: gemm_plan.h)
 #ifdef __HIPCC__
 // LDS image of a [key][64] matrix consumed TRANSPOSED as an MFMA A operand (16 head dims x 32 keys per fragment): V in the
 // attention forward, K / Q / dO in the backward.  Per (32-key chunk c, 16-dim block
@@ -203,8 +186,7 @@ struct GemmArgs {
     int ablate;         // developer builds only (-DGRIP_ABLATE, tools/mlp_ablation.sh): bit 0 = the c_fc epilogue issues no global store, bit 1 = the K = 4 d
                         // residual GEMM reads its A operand from a 31-MB window (Infinity-Cache resident); timing experiments, results are wrong by design
 };
-int gemm_pick_ksplit(int M, int N, int K);
-int gemm_pick_coop_split(int M, int N, int K);   // split factor of the cooperative form (1 = not worth it / not applicable)
+// gemm_pick_ksplit / gemm_pick_coop_split: gemm_plan.h
 
 int launch_gemm(int epi, const GemmArgs& a, hipStream_t s);
 int launch_gemm_f32(int epi, const GemmArgs& a, hipStream_t s);

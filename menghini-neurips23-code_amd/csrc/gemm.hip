@@ -17,9 +17,8 @@
 // accumulators are then transposed through a wave-private LDS slab so that bias / residual / C move as whole 128-byte
 // lines (epilogue_rows).  Workgroup ids are remapped so every XCD (private 4 MiB L2) owns a contiguous run of tiles,
 // N-fastest: the A row panel and the W panel stay L2-resident across the run.  The launcher picks the tile shape by
-// (relative rate) x (fill of the last wave of workgroups).
-#include <stdlib.h>
-
+// (relative rate) x (fill of the last wave of workgroups): gemm_plan.cpp.
+#include <type_traits>
 
 #include "common.h"
 
@@ -1408,101 +1407,6 @@ __global__ __launch_bounds__(NW * 64) void gemm_k64_kernel(GemmArgs g, int tiles
         epilogue_rows<EPI, RF, (EPI == EPI_BIAS_RESID_STATS || FOLD ? 1 : 2), FOLD>(g, acc[h], (float*)lds2 + wave * EPI_SLAB_FLOATS, m0 + wr * RF * 16, n0 + wc * WCOLS + h * 64, lane, pre, FOLD ? cb[h] : nullptr);
 }
 
-// ---- Developer prototype (r03): the 192x256 tile of gemm_k64_kernel with the stage feed on FOUR DEDICATED WAVES (12 waves per workgroup:
-// eight consumers of 96x64 -- 96 accumulator registers, ONE fragment set: three waves share a SIMD and 170 registers each -- and four
-// producers that issue the 56 DMA pieces of a stage and are the only ones to sit in the vector-memory issue stage).  Variant 9 of the
-// debug hook / GRIP_GEMM_BIG=9; one tile per workgroup.
-template <int EPI>
-__global__ __launch_bounds__(768) void gemm_k64w_kernel(GemmArgs g, int tiles_m, int tiles_n) {
-    constexpr int RF = 6, BMT = 32 * RF, BNT = 256;
-    constexpr int STAGE = (BMT + BNT) * BK;       // halfs per stage
-    constexpr int PIECES = (BMT + BNT) / 8;       // 56
-    constexpr int GP = PIECES / 4;                // per producer wave
-    extern __shared__ __attribute__((aligned(16))) half_t lds2[];
-
-    const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int tm = bid / tiles_n, tn = bid - tm * tiles_n;
-    const int m0 = tm * BMT, n0 = tn * BNT;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nk = g.K / BK;    // >= 2 (launcher)
-    const int rot = (k_rot(tn, tiles_n, nk) + tm * g.rot_rows) % nk;
-    auto ks = [&](int k) { return k + rot < nk ? k + rot : k + rot - nk; };
-
-    if (wave >= 8) {
-        const int pw = wave - 8;
-        const int srow = lane >> 3;
-        const int schunk = (lane & 7) ^ srow;
-        const size_t K = (size_t)g.K;
-        const uint32_t lane_off = 2u * ((uint32_t)srow * (uint32_t)g.K + (uint32_t)(schunk * 8));
-        auto stage = [&](int buf, int kt) {
-#pragma unroll
-            for (int i = 0; i < GP; ++i) {
-                const int pc = pw * GP + i;                   // piece: rows pc * 8 .. + 7 of the (A then W) stage
-                const half_t* row = pc * 8 < BMT ? (const half_t*)g.A + (size_t)(m0 + pc * 8) * K : (const half_t*)g.W + (size_t)(n0 + pc * 8 - BMT) * K;
-                __builtin_amdgcn_global_load_lds((const AS1 void*)((const char*)(row + (size_t)kt * BK) + lane_off), (AS3 void*)(lds2 + buf * STAGE + pc * 8 * BK), 16, 0, 0);
-            }
-        };
-        stage(0, ks(0));
-        stage(1, ks(1));
-        wait_vmcnt<GP>();
-        __builtin_amdgcn_s_barrier();                 // stage 0 landed
-        for (int kt = 0; kt < nk; ++kt) {
-            wait_vmcnt<0>();                          // stage kt + 1 landed
-            __builtin_amdgcn_s_barrier();             // ... and every consumer holds the last fragments of stage kt: its slot is free
-            if (kt + 2 < nk) stage(kt & 1, ks(kt + 2));
-        }
-        wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        return;
-    }
-
-    const int wr = wave >> 2, wc = wave & 3;
-    const int frow = lane & 15, fgrp = lane >> 4;
-    int a_off[2], b_off[2];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-        const int chunk = (kk * 4 + fgrp) ^ (lane & 7);
-        a_off[kk] = (wr * RF * 16 + frow) * BK + chunk * 8;
-        b_off[kk] = BMT * BK + (wc * 64 + frow) * BK + chunk * 8;
-    }
-    f32x4 acc[RF][4];
-    init_acc<EPI, RF>(g, acc, n0 + wc * 64, lane);
-    half8 fa[RF], fb[4];
-    auto rd = [&](int buf, int kk) {
-        const half_t* st = lds2 + buf * STAGE;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) fb[j] = *(const half8*)(st + b_off[kk] + j * 16 * BK);
-#pragma unroll
-        for (int i = 0; i < RF; ++i) fa[i] = *(const half8*)(st + a_off[kk] + i * 16 * BK);
-    };
-    auto mm = [&]() {
-#pragma unroll
-        for (int i = 0; i < RF; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb[j], fa[i], acc[i][j], 0, 0, 0);
-    };
-    __builtin_amdgcn_s_barrier();                     // stage 0 landed
-    for (int kt = 0; kt < nk; ++kt) {
-        const int buf = kt & 1;
-        rd(buf, 0);
-        mm();
-        rd(buf, 1);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                 // this stage's slot is free; stage kt + 1 has landed
-        mm();
-    }
-    __builtin_amdgcn_s_barrier();   // every consumer is done with the stages: reuse them as epilogue slabs
-    // (16-row passes: the operand prefetch of 32-row passes does not fit the 170-register budget of three waves per SIMD)
-    epilogue_rows<EPI, RF, 1>(g, acc, (float*)lds2 + wave * EPI_SLAB_FLOATS, m0 + wr * RF * 16, n0 + wc * 64, lane);
-}
-
 // ---- Persistent form of gemm_k64_kernel: one workgroup per CU walks its XCD's run of tiles, and the two-stage K pipeline
 // simply continues across tile boundaries -- the first two stages of tile t+1 are issued at the last two stage
 // boundaries of tile t and land while tile t's epilogue runs, so a tile no longer starts with an exposed HBM/L2 round trip
@@ -1835,108 +1739,114 @@ int launch_gemm(int epi, const GemmArgs& a, hipStream_t s) {
     return rc;
 }
 
-template <int BMT, int BNT, int NSTAGE>
-static int launch_big(int epi, const GemmArgs& a, hipStream_t s) {
-    const int tiles_m = (a.M + BMT - 1) / BMT, tiles_n = a.N / BNT;
-    constexpr size_t lds = (size_t)NSTAGE * (BMT + BNT) * BK2 * 2;
-    constexpr int threads = (BMT / 128) * (BNT / 64) * 64;
-    dim3 grid(tiles_m * tiles_n), block(threads);
-#define GRIP_GEMM_CASE(E)                                                                                                   \
-    case E: {                                                                                                               \
-        static bool configured = false;                                                                                     \
-        if (!configured) {                                                                                                  \
-            GRIP_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_big_kernel<E, BMT, BNT, NSTAGE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            configured = true;                                                                                              \
-        }                                                                                                                   \
-        hipLaunchKernelGGL((gemm_big_kernel<E, BMT, BNT, NSTAGE>), grid, block, lds, s, a, tiles_m, tiles_n);               \
-    } break;
+// ---- the launcher: gemm_plan (gemm_plan.cpp) decides, this launches what the plan says.
+// One epilogue dispatch for every kernel family: f(std::integral_constant<int, EPI>) for the run-time epilogue id.
+template <typename F>
+static int with_epi(int epi, F&& f) {
     switch (epi) {
-        GRIP_GEMM_CASE(EPI_F32)
-        GRIP_GEMM_CASE(EPI_BIAS_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_GELU_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_RESID)
-        GRIP_GEMM_CASE(EPI_F16)
-        GRIP_GEMM_CASE(EPI_GELUGRAD_F16)
-        GRIP_GEMM_CASE(EPI_F32_SCALE)
-        GRIP_GEMM_CASE(EPI_LNFOLD_F16)
-        GRIP_GEMM_CASE(EPI_LNFOLD_GELU_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_RESID_STATS)
+        case EPI_F32: return f(std::integral_constant<int, EPI_F32>{});
+        case EPI_BIAS_F16: return f(std::integral_constant<int, EPI_BIAS_F16>{});
+        case EPI_BIAS_GELU_F16: return f(std::integral_constant<int, EPI_BIAS_GELU_F16>{});
+        case EPI_BIAS_RESID: return f(std::integral_constant<int, EPI_BIAS_RESID>{});
+        case EPI_F16: return f(std::integral_constant<int, EPI_F16>{});
+        case EPI_GELUGRAD_F16: return f(std::integral_constant<int, EPI_GELUGRAD_F16>{});
+        case EPI_F32_SCALE: return f(std::integral_constant<int, EPI_F32_SCALE>{});
+        case EPI_LNFOLD_F16: return f(std::integral_constant<int, EPI_LNFOLD_F16>{});
+        case EPI_LNFOLD_GELU_F16: return f(std::integral_constant<int, EPI_LNFOLD_GELU_F16>{});
+        case EPI_BIAS_RESID_STATS: return f(std::integral_constant<int, EPI_BIAS_RESID_STATS>{});
         default: GRIP_REQUIRE(false, "gemm: unknown epilogue %d", epi);
     }
-#undef GRIP_GEMM_CASE
-    GRIP_CHECK_HIP(hipGetLastError());
-    return GRIP_OK;
 }
 
-template <int NW, int RF = 8>
-static int launch_k64(int epi, const GemmArgs& a, hipStream_t s) {
-    constexpr int BMT = 32 * RF;
-    const int tiles_m = (a.M + BMT - 1) / BMT, tiles_n = a.N / 256;
-    constexpr size_t lds = (size_t)2 * (BMT + 256) * BK * 2;
-    dim3 grid(tiles_m * tiles_n), block(NW * 64);
-#define GRIP_GEMM_CASE(E)                                                                                                   \
-    case E: {                                                                                                               \
-        static bool configured = false;                                                                                     \
-        if (!configured) {                                                                                                  \
-            GRIP_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_k64_kernel<E, NW, RF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            configured = true;                                                                                              \
-        }                                                                                                                   \
-        hipLaunchKernelGGL((gemm_k64_kernel<E, NW, RF>), grid, block, lds, s, a, tiles_m, tiles_n);                             \
-    } break;
-    switch (epi) {
-        GRIP_GEMM_CASE(EPI_F32)
-        GRIP_GEMM_CASE(EPI_BIAS_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_GELU_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_RESID)
-        GRIP_GEMM_CASE(EPI_F16)
-        GRIP_GEMM_CASE(EPI_GELUGRAD_F16)
-        GRIP_GEMM_CASE(EPI_F32_SCALE)
-        GRIP_GEMM_CASE(EPI_LNFOLD_F16)
-        GRIP_GEMM_CASE(EPI_LNFOLD_GELU_F16)
-        default: GRIP_REQUIRE(false, "gemm: unknown epilogue %d", epi);
+// One launch of one kernel instantiation on the plan's grid; the instantiation's dynamic-LDS limit is raised once, at its first launch.
+template <auto Kernel, typename... Extra>
+static int launch_planned(const GemmPlan& p, const GemmArgs& a, hipStream_t s, Extra... extra) {
+    static bool configured = false;
+    if (!configured && p.lds > 0) {
+        GRIP_CHECK_HIP(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
+        configured = true;
     }
-#undef GRIP_GEMM_CASE
+    hipLaunchKernelGGL(Kernel, dim3(p.grid_x, p.grid_y), dim3(p.block), (size_t)p.lds, s, a, p.tiles_m, p.tiles_n, extra...);
     GRIP_CHECK_HIP(hipGetLastError());
     return GRIP_OK;
 }
-
-static int launch_k64w(int epi, const GemmArgs& a, hipStream_t s) {
-    const int tiles_m = (a.M + 191) / 192, tiles_n = a.N / 256;
-    constexpr size_t lds = (size_t)2 * (192 + 256) * BK * 2;
-    dim3 grid(tiles_m * tiles_n), block(768);
-#define GRIP_GEMM_CASE(E)                                                                                                   \
-    case E: {                                                                                                               \
-        static bool configured = false;                                                                                     \
-        if (!configured) {                                                                                                  \
-            GRIP_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_k64w_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            configured = true;                                                                                              \
-        }                                                                                                                   \
-        hipLaunchKernelGGL((gemm_k64w_kernel<E>), grid, block, lds, s, a, tiles_m, tiles_n);                                \
-    } break;
-    switch (epi) {
-        GRIP_GEMM_CASE(EPI_F32)
-        GRIP_GEMM_CASE(EPI_BIAS_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_GELU_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_RESID)
-        GRIP_GEMM_CASE(EPI_GELUGRAD_F16)
-        default: GRIP_REQUIRE(false, "gemm: the loader-wave 192x256 prototype has no epilogue %d", epi);
-    }
-#undef GRIP_GEMM_CASE
-    GRIP_CHECK_HIP(hipGetLastError());
-    return GRIP_OK;
+static int no_instance(const GemmPlan& p) {
+    GRIP_REQUIRE(false, "gemm: the plan names a kernel that is not built (family %d, epilogue %d, %d-row tile)", (int)p.family, p.epi, p.tile_m);
 }
 
+// One helper per kernel family: the plan's template parameters -> the instantiation.  (The instantiated set is part of the product: every branch here is one.)
+static int launch_two_stage(const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
+    return with_epi(p.epi, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        return p.tile_m == 64 ? launch_planned<gemm_f16_kernel<E, 2>>(p, a, s) : launch_planned<gemm_f16_kernel<E, 4>>(p, a, s);
+    });
+}
+static int launch_ring(const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
+    return with_epi(p.epi, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        return p.nst == 3 ? launch_planned<gemm_ring_kernel<E, 3>>(p, a, s) : launch_planned<gemm_ring_kernel<E, 4>>(p, a, s);
+    });
+}
+// gemm_ringw_kernel: 32- and 64-row tiles run a 4-slot ring, 128-row tiles a 3-slot ring for short K walks and a 5-slot one (the whole LDS) for long
+// ones; the 96-row form (5 slots) exists for the residual and plain f16 epilogues only (the LayerNorm-folded ones fetch their row statistics with a
+// power-of-two lane map)
+static int launch_ringw(const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
+    return with_epi(p.epi, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        switch (p.tile_m) {
+            case 32: return launch_planned<gemm_ringw_kernel<E, 4, 1>>(p, a, s);
+            case 64: return launch_planned<gemm_ringw_kernel<E, 4, 2>>(p, a, s);
+            case 96:
+                if constexpr (E == EPI_BIAS_RESID || E == EPI_BIAS_RESID_STATS || E == EPI_F16) return launch_planned<gemm_ringw_kernel<E, 5, 3>>(p, a, s);
+                return no_instance(p);
+            case 128: return p.nst == 5 ? launch_planned<gemm_ringw_kernel<E, 5, 4>>(p, a, s) : launch_planned<gemm_ringw_kernel<E, 3, 4>>(p, a, s);
+        }
+        return no_instance(p);
+    });
+}
+static int launch_big(const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
+    return with_epi(p.epi, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        return p.tile_n == 256 ? launch_planned<gemm_big_kernel<E, 256, 256, 4>>(p, a, s) : launch_planned<gemm_big_kernel<E, 256, 128, 3>>(p, a, s);
+    });
+}
+static int launch_k64(const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
+    return with_epi(p.epi, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        if constexpr (E == EPI_BIAS_RESID_STATS) return no_instance(p);      // no registers left for the statistics: the plan sends them to the persistent kernel
+        else return p.tile_m == 192 ? launch_planned<gemm_k64_kernel<E, 8, 6>>(p, a, s) : launch_planned<gemm_k64_kernel<E, 8, 8>>(p, a, s);
+    });
+}
 #ifdef GRIP_ABLATE
 static int g_ablate = 0;
 extern "C" int grip_debug_ablate(int mask) { g_ablate = mask; return GRIP_OK; }
 #endif
-static int launch_k64p(int epi, const GemmArgs& a_in, hipStream_t s) {
+// gemm_k64p_kernel: epilogue forms 1 / 2 / 4 for the LayerNorm-folded epilogues, 1 for the residual + statistics one, and the single-block sub-step 1
+// (SD) for the default form of each of the three (GemmTuning::emode, ::sd)
+static int launch_k64p(const GemmPlan& p, const GemmArgs& a_in, hipStream_t s) {
     GemmArgs a = a_in;
 #ifdef GRIP_ABLATE
     a.ablate = g_ablate;
 #endif
-    const int tiles_m = (a.M + 255) / 256, tiles_n = a.N / 256;
-    constexpr size_t lds = (size_t)2 * 512 * BK * 2 + 8 * 4096;       // two stages + eight 4 KiB slabs = the whole 160 KiB
+    return with_epi(p.epi, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        if constexpr (E == EPI_LNFOLD_F16 || E == EPI_LNFOLD_GELU_F16) {
+            if (p.sd) return launch_planned<gemm_k64p_kernel<E, (E == EPI_LNFOLD_F16 ? 4 : 2), true>>(p, a, s, p.colgroup);
+            switch (p.emode) {
+                case 4: return launch_planned<gemm_k64p_kernel<E, 4>>(p, a, s, p.colgroup);
+                case 2: return launch_planned<gemm_k64p_kernel<E, 2>>(p, a, s, p.colgroup);
+                case 1: return launch_planned<gemm_k64p_kernel<E, 1>>(p, a, s, p.colgroup);
+            }
+        } else if constexpr (E == EPI_BIAS_RESID_STATS) {
+            if (p.sd) return launch_planned<gemm_k64p_kernel<E, 1, true>>(p, a, s, p.colgroup);
+            if (p.emode == 1) return launch_planned<gemm_k64p_kernel<E, 1>>(p, a, s, p.colgroup);
+        }
+        return launch_planned<gemm_k64p_kernel<E>>(p, a, s, p.colgroup);
+    });
+}
+
+// CUs a launch may use: the device's, in whole XCD rounds, cut by grip_set_cu_budget
+static int gemm_cu_count(int* n_cu) {
     static int n_cu_dev = 0;
     if (!n_cu_dev) {
         int dev = 0;
@@ -1945,451 +1855,42 @@ static int launch_k64p(int epi, const GemmArgs& a_in, hipStream_t s) {
         n_cu_dev &= ~7;
         GRIP_REQUIRE(n_cu_dev >= 8, "gemm: device reports %d CUs", n_cu_dev);
     }
-    int n_cu = n_cu_dev;
-    if (grip_cu_budget() > 0 && grip_cu_budget() < n_cu_dev) n_cu = grip_cu_budget() & ~7;     // the launch stream owns fewer CUs (grip_set_cu_budget)
-    const int tiles = tiles_m * tiles_n;
-    // every XCD owns ceil or floor(tiles_m / 8) row panels: the grid has enough workgroups per XCD for the largest band
-    const int band = ((tiles_m + 7) / 8) * tiles_n;
-    // Tile walk: the even N-fastest split (colgroup = 0) is the default.  The row-band / column-group walk (see the kernel) cuts
-    // the memory-side fetches of the K = 768 GEMMs by keeping one group's W panels L2-resident, but measured SLOWER on the
-    // pool encode (r02: c_fc 794 vs 839 TF/s, QKV 891 vs 922 with groups of 4 / 3 column tiles): the refetched W panels come
-    // out of the 256 MiB Infinity Cache, not HBM, and the banded walk makes all 32 workgroups of an XCD start their tiles'
-    // A panels at once.  GRIP_GEMM_COLGROUP=<n> (a divisor of N / 256; 1 = tiles_n wide bands) switches it on for A/B runs.
-    static const int force_cg = getenv("GRIP_GEMM_COLGROUP") ? atoi(getenv("GRIP_GEMM_COLGROUP")) : 0;
-    int colgroup = 0;
-    if (force_cg > 0 && tiles_m >= 64) {
-        colgroup = tiles_n;
-        if (a.K <= 1024 && force_cg > 1)
-            for (int c = force_cg; c >= 2; --c)
-                if (tiles_n % c == 0 && tiles_n > c) { colgroup = c; break; }
-    }
-    const int grid_n = colgroup ? (band * 8 >= n_cu ? n_cu : band * 8) : (tiles >= n_cu ? n_cu : ((tiles + 7) & ~7));
-    dim3 grid(grid_n), block(512);
-#define GRIP_GEMM_CASE(E)                                                                                                   \
-    case E: {                                                                                                               \
-        static bool configured = false;                                                                                     \
-        if (!configured) {                                                                                                  \
-            GRIP_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_k64p_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            configured = true;                                                                                              \
-        }                                                                                                                   \
-        hipLaunchKernelGGL((gemm_k64p_kernel<E>), grid, block, lds, s, a, tiles_m, tiles_n, colgroup);                                \
-    } break;
-#define GRIP_GEMM_CASE_M(E, MODE)                                                                                           \
-    case E: {                                                                                                               \
-        static bool configured = false;                                                                                     \
-        if (!configured) {                                                                                                  \
-            GRIP_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_k64p_kernel<E, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            configured = true;                                                                                              \
-        }                                                                                                                   \
-        hipLaunchKernelGGL((gemm_k64p_kernel<E, MODE>), grid, block, lds, s, a, tiles_m, tiles_n, colgroup);                          \
-    } break;
-    // Epilogue form of the three pool-encode epilogues: 0 = 8-byte stores through the f32 slab, 1 = 16-byte stores through the f32
-    // slab, 2 = direct with permuted W fragment rows, 4 = fold arithmetic in the fragment layout + double-buffered f16 slab (2 and 4:
-    // LayerNorm-folded epilogues only).  Default: QKV 4, c_fc 2, residual 1 -- measured in the loop (TF/s, one box): QKV 942 (1) /
-    // 929 (2) / 972 (4); c_fc 870 (1) / 892 (2) / 872 (4); residual 1 007 (1) / 954 (2).  GRIP_GEMM_EMODE=<m> forces one mode,
-    // three digits one each for QKV / c_fc / residual (developer A/B).
-    static const int emode_env = getenv("GRIP_GEMM_EMODE") ? atoi(getenv("GRIP_GEMM_EMODE")) : 421;
-    int emode = emode_env < 100 ? emode_env : (epi == EPI_LNFOLD_F16 ? emode_env / 100 : epi == EPI_LNFOLD_GELU_F16 ? (emode_env / 10) % 10 : emode_env % 10);
-    if (epi == EPI_BIAS_RESID_STATS && (emode == 2 || emode == 4)) emode = 1;
-    if (emode == 4 && a.out2) emode = 1;      // the f16-slab form has no pre-activation copy (train-mode forwards)
-    // single-block sub-step 1 (DMA pieces and fragment reads between the MFMAs) for the three default pool-encode instantiations:
-    // loop +0.9 %, residual GEMM 987 -> 1 010 TF/s, QKV 954 -> 966; GRIP_GEMM_SD=0 = the branchy form (developer A/B)
-    static const bool sd = !(getenv("GRIP_GEMM_SD") && atoi(getenv("GRIP_GEMM_SD")) == 0);
-#define GRIP_GEMM_CASE_SD(E, MODE)                                                                                          \
-    {                                                                                                                       \
-        static bool configured = false;                                                                                     \
-        if (!configured) {                                                                                                  \
-            GRIP_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_k64p_kernel<E, MODE, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            configured = true;                                                                                              \
-        }                                                                                                                   \
-        hipLaunchKernelGGL((gemm_k64p_kernel<E, MODE, true>), grid, block, lds, s, a, tiles_m, tiles_n, colgroup);                    \
-        GRIP_CHECK_HIP(hipGetLastError());                                                                                  \
-        return GRIP_OK;                                                                                                     \
-    }
-    if (sd && epi == EPI_LNFOLD_F16 && emode == 4) GRIP_GEMM_CASE_SD(EPI_LNFOLD_F16, 4)
-    if (sd && epi == EPI_LNFOLD_GELU_F16 && emode == 2) GRIP_GEMM_CASE_SD(EPI_LNFOLD_GELU_F16, 2)
-    if (sd && epi == EPI_BIAS_RESID_STATS && emode == 1) GRIP_GEMM_CASE_SD(EPI_BIAS_RESID_STATS, 1)
-#undef GRIP_GEMM_CASE_SD
-    if (emode != 0 && (epi == EPI_LNFOLD_F16 || epi == EPI_LNFOLD_GELU_F16 || epi == EPI_BIAS_RESID_STATS)) {
-        if (emode == 4 && epi != EPI_BIAS_RESID_STATS) {
-            switch (epi) {
-                GRIP_GEMM_CASE_M(EPI_LNFOLD_F16, 4)
-                GRIP_GEMM_CASE_M(EPI_LNFOLD_GELU_F16, 4)
-            }
-        } else if (emode == 2) {
-            switch (epi) {
-                GRIP_GEMM_CASE_M(EPI_LNFOLD_F16, 2)
-                GRIP_GEMM_CASE_M(EPI_LNFOLD_GELU_F16, 2)
-            }
-        } else {
-            switch (epi) {
-                GRIP_GEMM_CASE_M(EPI_LNFOLD_F16, 1)
-                GRIP_GEMM_CASE_M(EPI_LNFOLD_GELU_F16, 1)
-                GRIP_GEMM_CASE_M(EPI_BIAS_RESID_STATS, 1)
-            }
-        }
-        GRIP_CHECK_HIP(hipGetLastError());
-        return GRIP_OK;
-    }
-#undef GRIP_GEMM_CASE_M
-    switch (epi) {
-        GRIP_GEMM_CASE(EPI_F32)
-        GRIP_GEMM_CASE(EPI_BIAS_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_GELU_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_RESID)
-        GRIP_GEMM_CASE(EPI_F16)
-        GRIP_GEMM_CASE(EPI_GELUGRAD_F16)
-        GRIP_GEMM_CASE(EPI_F32_SCALE)
-        GRIP_GEMM_CASE(EPI_LNFOLD_F16)
-        GRIP_GEMM_CASE(EPI_LNFOLD_GELU_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_RESID_STATS)
-        default: GRIP_REQUIRE(false, "gemm: unknown epilogue %d", epi);
-    }
-#undef GRIP_GEMM_CASE
-    GRIP_CHECK_HIP(hipGetLastError());
-    return GRIP_OK;
-}
-
-// variant: 0 = choose, 1 = 128x128x64 (2-stage), 2 = 256x256x32 (4-stage ring), 3 = 256x128x32 (3-stage ring), 4 = 64x128x64 (2-stage),
-//          5 = 256x256x64 (2-stage, whole-line DMA), 6 = the same, persistent
-// Split-K factor for an EPI_F32 product whose output has too few 64x128 tiles while K is long (the input-gradient GEMMs of
-// the prompt steps: 136 tiles x 32 k-steps at M = 2 142, N = 512, K = 2 048): the SMALLEST factor that puts a workgroup on every
-// CU (>= 256 workgroups) with >= 4 k-steps each, and at least 2 below 512 tiles.  Measured (tools/small_gemm_bench.py,
-// SWEEP=1): text 15.5 us unsplit -> 11.7 at 2 = 11.7 at 4; image (324 tiles) 30.7 -> 24.7 at 2, 26.7 at 4 -- beyond one
-// workgroup per CU more partials only add traffic for the consumer (ln_bwd_add reads every partial).
-// Cooperative split-K of an epilogue-carrying GEMM (GemmArgs::coop_scratch): worth it when a handful of 64-row tiles walk a long K each -- every tile
-// stages its slices at the ~80 GB/s one CU pulls, whatever the other 200 CUs do.  The largest factor of {2, 4} (GRIP_COOP_SPLIT: developer A/B, 1 = off)
-// that leaves every split >= 4 slices and the launch <= 256 workgroups.
-int gemm_pick_coop_split(int M, int N, int K) {
-    static const int force = getenv("GRIP_COOP_SPLIT") ? atoi(getenv("GRIP_COOP_SPLIT")) : 0;
-    static const bool wspec = !(getenv("GRIP_GEMM_WSPEC") && atoi(getenv("GRIP_GEMM_WSPEC")) == 0);
-    if (!wspec) return 1;                          // the form lives in the loader-wave kernel only
-    const int64_t tiles = ((int64_t)((M + 63) / 64) * (N / BN) + 7) / 8 * 8;
-    const int nk = K / BK;
-    if (N % BN || K % BK || nk < 16 || tiles > 64) return 1;
-    if (force >= 1) return (nk % force == 0 && nk / force >= 3 && tiles * force <= 256) ? force : 1;
-    int best = 1;
-    for (int f : {2, 4})
-        if (nk % f == 0 && nk / f >= 4 && tiles * f <= 256) best = f;
-    return best;
-}
-
-int gemm_pick_ksplit(int M, int N, int K) {
-    static const int force = getenv("GRIP_GEMM_KSPLIT") ? atoi(getenv("GRIP_GEMM_KSPLIT")) : 0;   // developer A/B: 1 disables, n forces
-    const int64_t tiles = (int64_t)((M + 63) / 64) * (N / BN);
-    const int nk = K / BK;
-    if (force >= 1) return nk % force == 0 ? force : 1;
-    if (tiles >= 512) return 1;
-    // More 64-row tiles than CUs (the image tower's input-gradient GEMMs: M = 3 408, N = 768 -> 324): 128-row tiles instead, split so that
-    // about two of their 64-KiB workgroups share a CU -- the largest factor with <= 512 workgroups and >= 8 K tiles each.  VPT step in situ
-    // (tools/exp_r03_5.sh): 2 x 324 workgroups of 64x128 23.2 us, 2 x 162 of 128x128 23.2 us, 3 x 162 of 128x128 20.0 us (the third partial
-    // costs ln_bwd_add 1.5 us: 10.0 -> 11.5).
-    {
-        const int64_t t128 = (int64_t)((M + 127) / 128) * (N / BN);
-        if (tiles > 256 && t128 <= 256) {
-            int f128 = 1;
-            for (int f : {2, 3, 4})
-                if (nk % f == 0 && nk / f >= 8 && t128 * f <= 512) f128 = f;
-            if (f128 > 1) return f128;
-        }
-    }
-    int best = 1;
-    const int64_t t32 = (int64_t)((M + 31) / 32) * (N / BN);
-    for (int f : {2, 3, 4, 6, 8}) {
-        if (nk % f || nk / f < 3) continue;
-        best = f;                                   // a few dozen tiles (the shared-prefix text rows): as many K slices as keep 3 k-steps each
-        // workgroups of the launch: the launcher runs small launches on 32-row tiles (r06, launch_gemm_impl), which doubles them -- so half the splits already
-        // reach (nearly) every CU: M = 425, N = 512, K = 1 536 / 2 048: 4 splits x 56 tiles = 224 workgroups walking 6 - 8 slices instead of 8 x 28 walking 3 - 4,
-        // and ln_bwd_add sums 4 partials instead of 8 (graphed CoOp step 1.075 -> 1.041 ms, profiles/r06_ksplit_ab.txt)
-        const int64_t wgs = (tiles * f <= 128 && t32 * f <= 256) ? t32 * f : tiles * f;
-        if (nk / f >= 4 && wgs >= 224) break;       // the smallest factor that reaches (7/8 of) every CU
-    }
-    return best;
-}
-
-static int launch_ring(int epi, const GemmArgs& a, int nst, dim3 grid, hipStream_t s) {
-    const int tiles_m = (a.M + 63) / 64, tiles_n = a.N / BN;
-    const size_t lds = (size_t)nst * (64 + BN) * BK * 2;
-#define GRIP_GEMM_CASE(E)                                                                                                   \
-    case E: {                                                                                                               \
-        static bool configured = false;                                                                                     \
-        if (!configured) {                                                                                                  \
-            GRIP_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_ring_kernel<E, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (64 + BN) * BK * 2)); \
-            GRIP_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_ring_kernel<E, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (64 + BN) * BK * 2)); \
-            configured = true;                                                                                              \
-        }                                                                                                                   \
-        if (nst == 3) hipLaunchKernelGGL((gemm_ring_kernel<E, 3>), grid, dim3(256), lds, s, a, tiles_m, tiles_n);           \
-        else hipLaunchKernelGGL((gemm_ring_kernel<E, 4>), grid, dim3(256), lds, s, a, tiles_m, tiles_n);                    \
-    } break;
-    switch (epi) {
-        GRIP_GEMM_CASE(EPI_F32)
-        GRIP_GEMM_CASE(EPI_BIAS_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_GELU_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_RESID)
-        GRIP_GEMM_CASE(EPI_F16)
-        GRIP_GEMM_CASE(EPI_GELUGRAD_F16)
-        GRIP_GEMM_CASE(EPI_F32_SCALE)
-        GRIP_GEMM_CASE(EPI_LNFOLD_F16)
-        GRIP_GEMM_CASE(EPI_LNFOLD_GELU_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_RESID_STATS)
-        default: GRIP_REQUIRE(false, "gemm: unknown epilogue %d", epi);
-    }
-#undef GRIP_GEMM_CASE
-    GRIP_CHECK_HIP(hipGetLastError());
-    return GRIP_OK;
-}
-
-// gemm_ringw_kernel: WMF = 2 (64-row tiles) runs a 4-slot ring, WMF = 4 (128-row tiles) a 3-slot ring for short K walks and a 5-slot one
-// (the whole LDS) for long ones
-template <int WMF, int NST>
-static int launch_ringw(int epi, const GemmArgs& a, dim3 grid, hipStream_t s) {
-    constexpr int BMT = 32 * WMF;
-    const int tiles_m = (a.M + BMT - 1) / BMT, tiles_n = a.N / BN;
-    constexpr size_t lds = (size_t)NST * (BMT + BN) * BK * 2;
-    // the ring's prologue fills NST - 1 slots: the K walk (of one split) must be at least that long
-    GRIP_REQUIRE((a.K / BK) / (a.ksplit > 1 ? a.ksplit : 1) >= NST - 1, "gemm_ringw: K walk of %d tiles is shorter than the %d-slot ring's prologue", (a.K / BK) / (a.ksplit > 1 ? a.ksplit : 1), NST);
-#define GRIP_GEMM_CASE(E)                                                                                                   \
-    case E: {                                                                                                               \
-        static bool configured = false;                                                                                     \
-        if (!configured) {                                                                                                  \
-            GRIP_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_ringw_kernel<E, NST, WMF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            configured = true;                                                                                              \
-        }                                                                                                                   \
-        hipLaunchKernelGGL((gemm_ringw_kernel<E, NST, WMF>), grid, dim3(512), lds, s, a, tiles_m, tiles_n);                  \
-    } break;
-    switch (epi) {
-        GRIP_GEMM_CASE(EPI_F32)
-        GRIP_GEMM_CASE(EPI_BIAS_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_GELU_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_RESID)
-        GRIP_GEMM_CASE(EPI_F16)
-        GRIP_GEMM_CASE(EPI_GELUGRAD_F16)
-        GRIP_GEMM_CASE(EPI_F32_SCALE)
-        GRIP_GEMM_CASE(EPI_LNFOLD_F16)
-        GRIP_GEMM_CASE(EPI_LNFOLD_GELU_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_RESID_STATS)
-        default: GRIP_REQUIRE(false, "gemm: unknown epilogue %d", epi);
-    }
-#undef GRIP_GEMM_CASE
-    GRIP_CHECK_HIP(hipGetLastError());
-    return GRIP_OK;
-}
-
-// The 96-row form of the loader-wave ring (WMF = 3; r06): residual and plain f16 epilogues only (the LayerNorm-folded ones fetch their row statistics with a
-// power-of-two lane map).  For the K = 4 d residual GEMM of an image-tower prompt step -- M = 3 408, N = 768: 27 x 6 = 162 tiles of 128 rows leave 94 CUs idle for the whole
-// 48-slice walk; 36 x 6 = 216 tiles of 96 rows put 84 % of the chip on a walk that is a quarter shorter per tile.
-static int launch_ringw96(int epi, const GemmArgs& a, hipStream_t s) {
-    constexpr int NST = 5, WMF = 3, BMT = 96;
-    const int tiles_m = (a.M + BMT - 1) / BMT, tiles_n = a.N / BN;
-    constexpr size_t lds = (size_t)NST * (BMT + BN) * BK * 2;
-    GRIP_REQUIRE((int64_t)tiles_m * BMT <= a.m_pad && a.K / BK >= NST - 1 && a.ksplit <= 1, "gemm_ringw96: shape (M=%d K=%d m_pad=%lld ksplit=%d)", a.M, a.K, (long long)a.m_pad, a.ksplit);
-    dim3 grid(tiles_m * tiles_n);
-#define GRIP_GEMM_CASE(E)                                                                                                   \
-    case E: {                                                                                                               \
-        static bool configured = false;                                                                                     \
-        if (!configured) {                                                                                                  \
-            GRIP_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_ringw_kernel<E, NST, WMF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            configured = true;                                                                                              \
-        }                                                                                                                   \
-        hipLaunchKernelGGL((gemm_ringw_kernel<E, NST, WMF>), grid, dim3(512), lds, s, a, tiles_m, tiles_n);                  \
-    } break;
-    switch (epi) {
-        GRIP_GEMM_CASE(EPI_BIAS_RESID)
-        GRIP_GEMM_CASE(EPI_BIAS_RESID_STATS)
-        GRIP_GEMM_CASE(EPI_F16)
-        default: GRIP_REQUIRE(false, "gemm_ringw96: residual / plain f16 epilogues only (epi %d)", epi);
-    }
-#undef GRIP_GEMM_CASE
-    GRIP_CHECK_HIP(hipGetLastError());
+    *n_cu = (grip_cu_budget() > 0 && grip_cu_budget() < n_cu_dev) ? (grip_cu_budget() & ~7) : n_cu_dev;     // the launch stream owns fewer CUs
     return GRIP_OK;
 }
 
 static int launch_gemm_impl(int epi, const GemmArgs& a_in, hipStream_t s, int* chosen) {
-    // Row-dependent K rotation (GemmArgs::rot_rows = the caller's permission: train-mode launches only).  In a prompt step every GEMM
-    // reads weights nobody has touched since the previous step; with all tile rows of a column panel walking K in lockstep, each of them
-    // waits out the memory latency of every slice.  Staggered, a slice is fetched by one tile row and found in the L2 by the next: VPT
-    // step in situ (rocprofv3, tools/exp_r03_5.sh), GEMM time per step 2 245 us -> 2 025 us with a stride of 2 slices per tile row
-    // (1: 2 050, 3: 2 057, 5: 2 055, 11: 2 053); the split-K launches like 1 best (their walks are half or a third as long).
-    // GRIP_KROT_M: developer A/B (-1 = off, n > 0 = stride n).
-    static const int rot_m = getenv("GRIP_KROT_M") ? atoi(getenv("GRIP_KROT_M")) : 0;
+    GemmShape g{};
+    g.epi = epi; g.M = a_in.M; g.N = a_in.N; g.K = a_in.K; g.ldc = a_in.ldc; g.m_pad = a_in.m_pad;
+    g.variant = a_in.variant; g.ksplit = a_in.ksplit; g.f32 = a_in.f32; g.rot_rows = a_in.rot_rows;
+    g.stat_parts = a_in.stat_parts; g.split_stride = a_in.split_stride;
+    g.stat_part = a_in.stat_part; g.stat_in = a_in.stat_in; g.rowstat = a_in.rowstat; g.out2 = a_in.out2; g.coop = a_in.coop_scratch && a_in.coop_counter;
+    if (!a_in.f32) {
+        const int rc = gemm_cu_count(&g.n_cu);
+        if (rc) return rc;
+    }
+    const GemmPlan p = gemm_plan(g, gemm_tuning());
+    if (p.status) {
+        grip_set_error("%s", p.msg);
+        return p.status;
+    }
+    *chosen = p.variant;
     GemmArgs a = a_in;
-    a.rot_rows = (a.rot_rows && !a.f32 && rot_m >= 0) ? (rot_m > 0 ? rot_m : (a.ksplit > 1 ? 1 : 2)) : 0;
-    if (a.f32 == 2) {   // split-f16 tier (gemm_split.hip); profiler variant 7
-        *chosen = 7;
-        return launch_gemm_split(epi, a, s);
-    }
-    if (a.f32) {        // exact mode: f32 operands (gemm_f32.hip); profiler variant 0
-        *chosen = 0;
-        return launch_gemm_f32(epi, a, s);
-    }
-    if (epi == EPI_BIAS_RESID && a.stat_part) epi = EPI_BIAS_RESID_STATS;
-    GRIP_REQUIRE(epi != EPI_BIAS_RESID_STATS || (a.stat_part && a.N % 64 == 0), "gemm: row statistics need stat_part and N %% 64 == 0");
-    GRIP_REQUIRE(a.N % BN == 0 && a.K % BK == 0 && a.M > 0, "gemm: need N %% 128 == 0 and K %% 64 == 0 (M=%d N=%d K=%d)", a.M, a.N, a.K);
-    GRIP_REQUIRE(a.ldc % 4 == 0, "gemm: ldc %% 4 != 0");
-    GRIP_REQUIRE(((int64_t)a.M + 256) * a.ldc < ((int64_t)1 << 31), "gemm: output larger than 2^31 elements (M=%d ldc=%d)", a.M, a.ldc);
-    const int64_t m256 = (int64_t)((a.M + 255) / 256) * 256;
-    const bool can_big = a.m_pad >= m256 && a.K >= 4 * BK2;       // A must be padded to the 256-row tile
-    int variant = a.variant;
-    if (variant == 0) {
-        // pick the tile shape by (measured relative rate) x (fill of the last wave of workgroups over
-        // 256 CUs): 256x256 runs one workgroup per CU, the other two shapes two per CU.
-        auto fill = [](int64_t tiles, int64_t slots) { return (double)tiles / (double)(((tiles + slots - 1) / slots) * slots); };
-        const int64_t tm128 = (a.M + 127) / 128, tm256 = m256 / 256;
-        double best = 0.85 * fill(tm128 * (a.N / 128), 512);
-        variant = 1;
-        {
-            double s4 = 0.70 * fill((int64_t)((a.M + 63) / 64) * (a.N / 128), 768);   // three 48-KiB workgroups per CU
-            // fewer 128-row tiles than CUs: the launch is one workgroup per CU whatever the shape, and its time is k-steps x (bytes
-            // a CU stages per step), which the 64-row tile cuts by a quarter (measured at M = 425 and 2 142: 6-25 % faster)
-            if (tm128 * (a.N / 128) <= 256) s4 = 1.0;
-            if (s4 > best) { best = s4; variant = 4; }
-            // ... unless the 64-row tiles outnumber the CUs while the 128-row ones do not: one round of 128-row tiles on dedicated loader
-            // waves (gemm_ringw_kernel) beats a round and a bit of 64-row ones (M = 3 408, N = 768, K = 3 072: 25.6 us against 31)
-            static const bool r128 = !(getenv("GRIP_GEMM_R128") && atoi(getenv("GRIP_GEMM_R128")) == 0);     // developer A/B
-            if (r128 && variant == 4 && a.ksplit <= 1 && tm128 * (a.N / 128) <= 256 && (int64_t)((a.M + 63) / 64) * (a.N / 128) > 256 && a.K > 12 * BK) { best = 1.0; variant = 1; }
-        }
-        if (can_big) {
-            const double s3 = 0.93 * fill(tm256 * (a.N / 128), 512);
-            if (s3 > best) { best = s3; variant = 3; }
-            if (a.N % 256 == 0) {
-                const double s2 = 1.0 * fill(tm256 * (a.N / 256), 256);
-                // same tile, two feeds: the 64-wide two-stage kernel (whole-line DMA) is 2-6 % faster than the 32-wide ring
-                // ... and persistent (one workgroup per CU walking its XCD's tiles) once every CU gets several tiles
-                static const int force = getenv("GRIP_GEMM_BIG") ? atoi(getenv("GRIP_GEMM_BIG")) : 0;    // developer A/B: 2, 5 or 6
-                if (s2 > best) { best = s2; variant = force ? force : (a.K < 2 * BK ? 2 : (tm256 * (a.N / 256) >= 512 ? 6 : 5)); }
-                // fewer tiles than CUs: one tile-time whatever the tile holds, so the 192-row form of the same kernel when it fills more CUs
-                const int64_t tm192 = (a.M + 191) / 192;
-                if (variant == 5 && !force && tm192 * 192 <= a.m_pad && tm192 * (a.N / 256) <= 256 && epi != EPI_BIAS_RESID_STATS &&
-                    fill(tm192 * (a.N / 256), 256) > best) { best = fill(tm192 * (a.N / 256), 256); variant = 8; }
-            }
-        }
-    }
-    const int ksplit = a.ksplit > 1 ? a.ksplit : 1;
-    const bool coop = ksplit > 1 && (epi == EPI_BIAS_RESID || epi == EPI_BIAS_RESID_STATS);
-    if (coop) {     // cooperative split-K: loader-wave kernel on 64-row tiles only (GemmArgs::coop_scratch)
-        const int64_t t64 = (int64_t)((a.M + 63) / 64) * (a.N / BN);
-        GRIP_REQUIRE(a.coop_scratch && a.coop_counter && (a.K / BK) % ksplit == 0 && (a.K / BK) / ksplit >= 3 && ((t64 + 7) / 8 * 8) * ksplit <= 256,
-                     "gemm: cooperative split-K needs the scratch and counter buffers, (K/64) %% ksplit == 0 with >= 3 slices per split and <= 256 workgroups (M=%d N=%d K=%d ksplit=%d)",
-                     a.M, a.N, a.K, ksplit);
-        variant = 4;
-    } else if (ksplit > 1) {
-        GRIP_REQUIRE(epi == EPI_F32 && (a.K / BK) % ksplit == 0 && a.split_stride >= (int64_t)a.M * a.ldc,
-                     "gemm: split-K needs EPI_F32, (K/64) %% ksplit == 0 and a partial stride >= M*ldc (K=%d ksplit=%d)", a.K, ksplit);
-        // 128-row tiles where gemm_pick_ksplit sized the split for them (more 64-row tiles than CUs: about two 128-row workgroups per CU)
-        const int64_t t64 = (int64_t)((a.M + 63) / 64) * (a.N / BN), t128 = (int64_t)((a.M + 127) / 128) * (a.N / BN);
-        if (a.variant == 0 && t64 > 256 && t128 * ksplit <= 512) variant = 1;
-        else if (variant != 1) variant = 4;
-    }
-    if (variant == 5 && epi == EPI_BIAS_RESID_STATS) variant = 6;   // the one-tile-per-workgroup 64-wide kernel has no registers left for the statistics
-    *chosen = variant;
-    // At most one workgroup per CU: the ring with the feed on its own waves (gemm_ringw_kernel).  GRIP_GEMM_WSPEC=0: developer A/B.
-    static const bool wspec = !(getenv("GRIP_GEMM_WSPEC") && atoi(getenv("GRIP_GEMM_WSPEC")) == 0);
-    GRIP_REQUIRE(a.stat_parts <= 0 || a.stat_in, "gemm: stat_parts without stat_in");      // (every kernel but the persistent one reads the partial sums itself: row_stat)
-    if (a.stat_parts > 0 && variant == 6) {      // the persistent kernel (pool-sized M) takes finalised statistics only
-        GRIP_REQUIRE(a.rowstat, "gemm: partial row sums on the persistent kernel need a rowstat buffer to finalise into");
+    a.rot_rows = p.rot_rows;
+    if (p.finalize_stats) {      // the persistent kernel takes finalised statistics only
         const int rc = launch_ln_stats_finalize(a.stat_in, a.stat_parts, const_cast<float*>(a.rowstat), a.M, a.K, s);
         if (rc) return rc;
         a.stat_parts = 0;
     }
-    if (variant == 2) {
-        GRIP_REQUIRE(can_big && a.N % 256 == 0, "gemm: 256x256 tile needs N %% 256 == 0 and A padded to 256 rows");
-        return launch_big<256, 256, 4>(epi, a, s);
+    switch (p.family) {
+        case GEMM_SPLIT: return launch_gemm_split(epi, a, s);
+        case GEMM_F32: return launch_gemm_f32(epi, a, s);
+        case GEMM_TWO_STAGE: return launch_two_stage(p, a, s);
+        case GEMM_RING: return launch_ring(p, a, s);
+        case GEMM_RINGW: return launch_ringw(p, a, s);
+        case GEMM_BIG: return launch_big(p, a, s);
+        case GEMM_K64: return launch_k64(p, a, s);
+        case GEMM_K64P: return launch_k64p(p, a, s);
     }
-    if (variant == 3) {
-        GRIP_REQUIRE(can_big, "gemm: 256x128 tile needs A padded to 256 rows");
-        return launch_big<256, 128, 3>(epi, a, s);
-    }
-    if (variant == 5) {
-        GRIP_REQUIRE(can_big && a.N % 256 == 0 && a.K >= 2 * BK, "gemm: 256x256x64 tile needs N %% 256 == 0, K >= 128 and A padded to 256 rows");
-        return launch_k64<8>(epi, a, s);
-    }
-    if (variant == 6) {
-        GRIP_REQUIRE(can_big && a.N % 256 == 0 && a.K >= 2 * BK, "gemm: 256x256x64 tile needs N %% 256 == 0, K >= 128 and A padded to 256 rows");
-        return launch_k64p(epi, a, s);
-    }
-    {
-        static const bool k64w = getenv("GRIP_K64W") && atoi(getenv("GRIP_K64W")) != 0;     // developer A/B
-        if (k64w && variant == 8 && (epi == EPI_BIAS_GELU_F16 || epi == EPI_GELUGRAD_F16)) variant = 9;
-    }
-    if (variant == 9) {      // developer prototype: 192x256 tile with loader waves
-        GRIP_REQUIRE(a.N % 256 == 0 && a.K >= 2 * BK && (int64_t)((a.M + 191) / 192) * 192 <= a.m_pad, "gemm: 192x256x64 loader-wave tile: shape");
-        return launch_k64w(epi, a, s);
-    }
-    if (variant == 8) {      // (7 is the f32 kernel in the debug hook)
-        GRIP_REQUIRE(a.N % 256 == 0 && a.K >= 2 * BK && (int64_t)((a.M + 191) / 192) * 192 <= a.m_pad && epi != EPI_BIAS_RESID_STATS,
-                     "gemm: 192x256x64 tile needs N %% 256 == 0, K >= 128, A padded to a multiple of 192 rows and an epilogue without row statistics");
-        return launch_k64<8, 6>(epi, a, s);
-    }
-    const int bmt = variant == 4 ? 64 : 128;
-    const int tiles_m = (a.M + bmt - 1) / bmt, tiles_n = a.N / BN;
-    dim3 grid(tiles_m * tiles_n, ksplit), block(256);
-    if (coop) {
-        GRIP_REQUIRE(wspec, "gemm: cooperative split-K needs the loader-wave kernels (GRIP_GEMM_WSPEC=0 is set)");
-        grid.x = (grid.x + 7) / 8 * 8;       // the splits of a tile on one XCD (gemm_ringw_kernel)
-        return launch_ringw<2, 4>(epi, a, grid, s);
-    }
-    {   // the 96-row loader-wave tile also for SHORT walks whose 64-row tiles outnumber the CUs (M = 3 408, N = K = 768 -- the out-proj forward of an image-tower
-        // prompt step and its input gradient: 324 tiles of 64 rows at two workgroups per CU against 216 of 96 rows at one: VPT step 2.82 -> 2.78 ms, UPT
-        // 3.15 -> 3.12, profiles/r06_r96_ab.txt).  GRIP_GEMM_R96 (developer A/B): 0 = no 96-row tiles, 1 = long walks only, 2 (default) = both
-        static const int r96mode = getenv("GRIP_GEMM_R96") ? atoi(getenv("GRIP_GEMM_R96")) : 2;
-        const int64_t t96 = (int64_t)((a.M + 95) / 96) * (a.N / BN), t64 = (int64_t)((a.M + 63) / 64) * (a.N / BN);
-        if (r96mode >= 2 && wspec && ksplit == 1 && a.variant == 0 && variant == 4 && (epi == EPI_BIAS_RESID || epi == EPI_BIAS_RESID_STATS || epi == EPI_F16) &&
-            t96 <= 256 && t64 > 256 && (int64_t)((a.M + 95) / 96) * 96 <= a.m_pad && a.K / BK >= 4)
-            return launch_ringw96(epi, a, s);
-    }
-    if (wspec && (int64_t)grid.x * ksplit <= 256) {
-        const int nk = a.K / BK / ksplit;
-        {   // 32-row tiles (WMF = 1; r06) where the 64-row ones fill at most half the chip -- the text tower's M = 425 GEMMs of a CoOp step: 28 - 112 tiles of 64 rows
-            // become 56 - 224 of 32 rows, each staging 160 instead of 192 rows per K slice through its CU's LDS-DMA path: graphed CoOp step 1.11 - 1.16 -> 1.076 ms
-            // (profiles/r06_r32_ab.txt).  Same products in the same order: bit-identical (tests/test_gpu_kernels.py).  GRIP_GEMM_R32=0: developer A/B
-            static const bool r32 = !(getenv("GRIP_GEMM_R32") && atoi(getenv("GRIP_GEMM_R32")) == 0);
-            const int64_t t32 = (int64_t)((a.M + 31) / 32) * (a.N / BN);
-            // (split-K input-gradient GEMMs too -- EPI_F32 partials, one grid row per split -- as long as all splits of the 32-row tiles still fit one per CU)
-            if (r32 && variant == 4 && nk >= 3 && !coop && (ksplit == 1 || epi == EPI_F32) && a.variant == 0 && (int64_t)grid.x * ksplit <= 128 && t32 * ksplit <= 256) {
-                dim3 g32((unsigned)t32, (unsigned)ksplit);
-                return launch_ringw<1, 4>(epi, a, g32, s);
-            }
-        }
-        if (variant == 4 && nk >= 3) return launch_ringw<2, 4>(epi, a, grid, s);
-        if (variant == 1 && nk > 12 && ksplit == 1 && a.variant == 0 && (epi == EPI_BIAS_RESID || epi == EPI_BIAS_RESID_STATS)) {
-            // long walk, residual epilogue, fewer 128-row tiles than CUs: the 96-row form when it fills more of them (and its rows are allocated)
-            static const bool r96 = !(getenv("GRIP_GEMM_R96") && atoi(getenv("GRIP_GEMM_R96")) == 0);     // developer A/B
-            const int64_t t96 = (int64_t)((a.M + 95) / 96) * (a.N / BN);
-            if (r96 && t96 <= 256 && t96 > (int64_t)grid.x && (int64_t)((a.M + 95) / 96) * 96 <= a.m_pad) return launch_ringw96(epi, a, s);
-        }
-        if (variant == 1 && nk > 12) return launch_ringw<4, 5>(epi, a, grid, s);
-        if (variant == 1 && nk >= 2) return launch_ringw<4, 3>(epi, a, grid, s);
-    }
-
-    if (variant == 4) {
-        // ring depth by workgroups per CU: <= 1 -> four stages (96 KiB), <= 2 -> three (72 KiB, two per CU); beyond that three
-        // co-resident two-stage workgroups already keep three tiles in flight per CU
-        static const int force = getenv("GRIP_GEMM_RING") ? atoi(getenv("GRIP_GEMM_RING")) : -1;    // developer A/B: 0 (off), 3, 4
-        const int64_t wgs = (int64_t)grid.x * ksplit;
-        const int nk = a.K / BK / ksplit;
-        int nst = force >= 0 ? force : (wgs <= 256 ? 4 : (wgs <= 512 ? 3 : 0));
-        if (nst && nk < nst - 1) nst = 0;
-        if (nst) return launch_ring(epi, a, nst, grid, s);
-    }
-#define GRIP_GEMM_CASE(E)                                                                                  \
-    case E:                                                                                                \
-        if (variant == 4) hipLaunchKernelGGL((gemm_f16_kernel<E, 2>), grid, block, 0, s, a, tiles_m, tiles_n); \
-        else hipLaunchKernelGGL((gemm_f16_kernel<E, 4>), grid, block, 0, s, a, tiles_m, tiles_n);          \
-        break;
-    switch (epi) {
-        GRIP_GEMM_CASE(EPI_F32)
-        GRIP_GEMM_CASE(EPI_BIAS_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_GELU_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_RESID)
-        GRIP_GEMM_CASE(EPI_F16)
-        GRIP_GEMM_CASE(EPI_GELUGRAD_F16)
-        GRIP_GEMM_CASE(EPI_F32_SCALE)
-        GRIP_GEMM_CASE(EPI_LNFOLD_F16)
-        GRIP_GEMM_CASE(EPI_LNFOLD_GELU_F16)
-        GRIP_GEMM_CASE(EPI_BIAS_RESID_STATS)
-        default: GRIP_REQUIRE(false, "gemm: unknown epilogue %d", epi);
-    }
-#undef GRIP_GEMM_CASE
-    GRIP_CHECK_HIP(hipGetLastError());
-    return GRIP_OK;
+    return no_instance(p);
 }

@@ -4,7 +4,9 @@
 //   * grip_leaderboard_scan_bounded with the worker-thread pre-filter (n * c >= 4 M), several refinement rounds, every result compared with the
 //     single-threaded scan of the same inputs (marks, lists) and, once everything is final, with grip_leaderboard_scan;
 //   * grip_bpe_* on a synthetic merges table: concurrent encodes through one handle (the per-word cache under its mutex), malformed tables,
-//     truncated inputs, output buffers that are too small.
+//     truncated inputs, output buffers that are too small;
+//   * grip_debug_gemm_plan (csrc/gemm_plan.cpp, the GEMM launcher's decision) over a grid of small and large M, N, K, split factors and flag
+//     combinations, the largest shapes an int holds included: the tile-count products must not overflow.
 // The reference has no such code (its scan is a Python loop, utils/clip_pseudolabels.py:49-112; its tokenizer is third-party Python).
 #include <math.h>
 #include <stdint.h>
@@ -18,6 +20,7 @@
 #include <vector>
 
 #include "../../include/grip_amd.h"
+#include "../../include/grip_amd_debug.h"
 
 static int fails = 0;
 #define CHECK(c, ...) do { if (!(c)) { ++fails; fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); } } while (0)
@@ -201,6 +204,35 @@ static void bpe_cases() {
     printf("bpe: %zu words x 8 threads, texts, short buffers, %zu malformed tables\n", words.size(), sizeof(broken) / sizeof(broken[0]) + 2);
 }
 
+static void gemm_plan_cases() {
+    const int dims_m[] = {1, 16, 63, 64, 65, 425, 3408, 50000, 260040, 300000, 1 << 24, 2147483647 - 300, 2147483647, 0, -5};
+    const int dims_n[] = {128, 256, 384, 768, 3072, 4096, 1 << 20, 2147483520, 0, 100};
+    const int dims_k[] = {64, 128, 192, 768, 832, 3072, 4096, 1 << 20, 2147483584, 0, 96};
+    char text[512];
+    long ok = 0, refused = 0;
+    for (int M : dims_m)
+        for (int N : dims_n)
+            for (int K : dims_k)
+                for (int epi = -1; epi <= 10; ++epi)
+                    for (int variant = 0; variant <= 9; ++variant)
+                        for (int ksplit : {0, 1, 2, 3, 4, 8, 1 << 30, -1})
+                            for (int present : {0, 1, 6, 8, 16, 31}) {
+                                const int64_t pads[] = {M, ((int64_t)M + 255) / 256 * 256, ((int64_t)M + 767) / 768 * 768};
+                                const int64_t m_pad = pads[(epi + variant + 2) % 3];
+                                const int ldc = (variant & 1) ? N : N / 8 * 4 + (epi == 5 ? 2 : 0);
+                                const int f32 = (epi == 10) ? 1 + (variant & 1) : 0;
+                                text[0] = 0;
+                                const int rc = grip_debug_gemm_plan(epi, M, N, K, ldc, m_pad, variant, ksplit, f32, present & 1, present, (present & 2) ? N / 64 : (variant == 9 ? 3 : 0),
+                                                                    (int64_t)m_pad * ldc, (variant & 2) ? 256 : 192, text, (int)sizeof text);
+                                CHECK(rc == 0 || rc == GRIP_ERR_ARG, "gemm_plan: status %d", rc);
+                                CHECK(text[0] != 0 && strlen(text) < sizeof text, "gemm_plan: no text");
+                                if (rc == 0) ++ok; else ++refused;
+                            }
+    CHECK(grip_debug_gemm_plan(1, 425, 512, 512, 512, 512, 0, 0, 0, 0, 0, 0, 0, 256, text, 8) == 0 && strlen(text) == 7, "gemm_plan: a short text buffer must be cut, not overrun");
+    CHECK(grip_debug_gemm_plan(1, 425, 512, 512, 512, 512, 0, 0, 0, 0, 0, 0, 0, 256, nullptr, 0) == 0, "gemm_plan: no text buffer");
+    printf("gemm_plan: %ld plans, %ld refused shapes\n", ok, refused);
+}
+
 int main() {
     // (n * c >= 4 M switches the worker-thread pre-filter on: 40 000 x 102 and 70 000 x 64)
     scan_case("near-tied, dominant class", 40000, 102, 0.05, 4e-3, 1, true, 16);
@@ -215,6 +247,7 @@ int main() {
     scan_case("log-odds, label everything", 40000, 102, 2.0, 1e-2, 13, false, 10000000, 1);
     scan_case("log-odds, small", 3000, 10, 3.0, 5e-2, 14, false, 3, 1);
     bpe_cases();
+    gemm_plan_cases();
     if (fails) { fprintf(stderr, "%d check(s) failed\n", fails); return 1; }
     printf("sanitize driver: all checks passed\n");
     return 0;

@@ -303,7 +303,7 @@ def test_grip_schedule_matches_the_reference_formula():
 
 
 def test_cooperative_split_factor_choice():
-    """Host-side shape logic of the cooperative split-K GEMM (csrc/gemm.hip, gemm_pick_coop_split; no GPU needed): used for a few dozen 64 x 128 tiles walking
+    """Host-side shape logic of the cooperative split-K GEMM (csrc/gemm_plan.cpp, gemm_pick_coop_split; no GPU needed): used for a few dozen 64 x 128 tiles walking
     >= 16 K slices (the text tower's c_proj in a prompt step), never for launches that fill the chip on their own."""
     import grip_amd  # noqa: F401
     from grip_amd import native
