@@ -281,6 +281,25 @@ int grip_upt_mixer_backward_deep(const grip_upt_mixer* m, const float* vpt_deep,
                                  size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 9 additions) MaPLe coupling function (models/prompts_models.py MaPLeModel; csrc/couple.hip): every visual prompt is a trainable Linear of
+ * the text prompt of the same depth, independent weights per depth.  All tensors f32, device, 16-byte aligned.
+ *   ctx          [P, text_width]                      the shallow text context
+ *   deep_text    [n_deep, P, text_width]              the deep text prompts of blocks 1 .. n_deep (null when n_deep == 0)
+ *   w            [1 + n_deep, vision_width, text_width], b [1 + n_deep, vision_width]      nn.Linear layout (y = x W^T + b); row 0 = shallow, row l = block l
+ *   vis_prefix   [P, vision_width] = ctx w[0]^T + b[0];   vis_deep [n_deep, P, vision_width], vis_deep[l - 1] = deep_text[l - 1] w[l]^T + b[l]
+ *   backward: d_vis_prefix / d_vis_deep (what grip_vit_backward_deep returns) -> d_w[l] = dY[l]^T X[l], d_b[l] = sum_p dY[l][p], d_ctx / d_deep_text = dY[l] w[l]
+ *             (the coupling's share only: the text tower's gradient of the same tensors is added by the caller).
+ *   P 1 .. 16, n_deep 0 .. 31, widths multiples of 64 up to 1024.  One launch forward; two backward (w is read once, d_w written once; the second launch
+ *   adds the partial d_ctx / d_deep_text of the workspace in a fixed order: no atomics, bit-reproducible).  workspace: grip_prompt_couple_workspace bytes,
+ *   scratch of the backward only. */
+int grip_prompt_couple_workspace(int n_prompt, int n_deep, int text_width, int vision_width, size_t* bytes);
+int grip_prompt_couple_forward(const float* ctx, const float* deep_text, int n_prompt, int n_deep, int text_width, int vision_width, const float* w,
+                               const float* b, float* vis_prefix, float* vis_deep, void* stream);
+int grip_prompt_couple_backward(const float* ctx, const float* deep_text, int n_prompt, int n_deep, int text_width, int vision_width, const float* w,
+                                const float* d_vis_prefix, const float* d_vis_deep, float* d_ctx, float* d_deep_text, float* d_w, float* d_b,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CLIP preprocessing of one decoded image: the `_transform` the reference applies per item on the host
  * (data/dataset.py:64-79 via clip.load's preprocess): Resize(n_px, BICUBIC) -> CenterCrop(n_px) -> ToTensor -> Normalize.
  * Bit-exact with Pillow's 8-bit bicubic resample; only the cropped rows / columns are produced.

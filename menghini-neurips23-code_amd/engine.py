@@ -647,6 +647,64 @@ class UptMixerFn(torch.autograd.Function):
         return tuple(gr.reshape(sh).to(dtp) for gr, sh, dtp in zip(grads, ctx.shapes, ctx.dtypes))
 
 
+def _couple_dims(ctx, deep, w, b):
+    """(P, D, dt, dv) of a coupling call; ctx [P, dt] or [1, P, dt], deep None or [D, P, dt], w [1 + D, dv, dt], b [1 + D, dv]."""
+    P, dt = ctx.shape[-2], ctx.shape[-1]
+    D = 0 if deep is None else deep.shape[0]
+    if ctx.numel() != P * dt or w.dim() != 3 or w.shape[0] != 1 + D or w.shape[2] != dt or tuple(b.shape) != (1 + D, w.shape[1]) \
+            or (deep is not None and tuple(deep.shape) != (D, P, dt)):
+        raise native.GripError(f"prompt coupling: ctx {tuple(ctx.shape)}, deep_text {None if deep is None else tuple(deep.shape)}, w {tuple(w.shape)}, "
+                               f"b {tuple(b.shape)}: expected [P, dt], [D, P, dt], [1 + D, dv, dt], [1 + D, dv]")
+    return P, D, dt, w.shape[1]
+
+
+def prompt_couple_forward(ctx, deep_text, w, b):
+    """MaPLe's coupling function on the native kernel (csrc/couple.hip), no autograd: (vis_prefix [P, dv], vis_deep [D, P, dv] or None)."""
+    lib = native.lib()
+    ctx, w, b = (t.detach().contiguous().float() for t in (ctx, w, b))
+    deep = None if deep_text is None else deep_text.detach().contiguous().float()
+    P, D, dt, dv = _couple_dims(ctx, deep, w, b)
+    vis_prefix = torch.empty(P, dv, dtype=torch.float32, device=ctx.device)
+    vis_deep = torch.empty(D, P, dv, dtype=torch.float32, device=ctx.device) if D else None
+    native.check(lib.grip_prompt_couple_forward(_ptr(ctx), _ptr(deep), P, D, dt, dv, _ptr(w), _ptr(b), _ptr(vis_prefix), _ptr(vis_deep), _stream()))
+    return vis_prefix, vis_deep
+
+
+class PromptCoupleFn(torch.autograd.Function):
+    """MaPLe's coupling function with native forward and backward: (ctx, deep_text or None, w, b) -> (vis_prefix, vis_deep) -- vis_prefix alone
+    when deep_text is None -- and the gradients of all four.  The gradient of ctx / deep_text is the coupling's share; autograd adds the text
+    tower's (TextPrefixFn) on the same leaves."""
+
+    @staticmethod
+    def forward(ctx_, ctx, deep_text, w, b):
+        ts = [None if t is None else t.detach().contiguous().float() for t in (ctx, deep_text, w, b)]
+        ctx_.dims = _couple_dims(ts[0], ts[1], ts[2], ts[3])
+        ctx_.meta = [None if t is None else (t.shape, t.dtype) for t in (ctx, deep_text, w, b)]
+        ctx_.save_for_backward(*[t for t in ts[:3] if t is not None])
+        vis_prefix, vis_deep = prompt_couple_forward(*ts)
+        return vis_prefix if vis_deep is None else (vis_prefix, vis_deep)
+
+    @staticmethod
+    def backward(ctx_, d_prefix, d_deep=None):
+        lib = native.lib()
+        P, D, dt, dv = ctx_.dims
+        saved = ctx_.saved_tensors
+        x, deep, w = (saved[0], saved[1], saved[2]) if D else (saved[0], None, saved[1])
+        dev = x.device
+        d_prefix = torch.zeros(P, dv, device=dev) if d_prefix is None else d_prefix.contiguous().float()
+        if D:
+            d_deep = torch.zeros(D, P, dv, device=dev) if d_deep is None else d_deep.contiguous().float()
+        g_x, g_w = torch.empty_like(x), torch.empty_like(w)
+        g_deep = torch.empty_like(deep) if D else None
+        g_b = torch.empty(1 + D, dv, dtype=torch.float32, device=dev)
+        nbytes = c_size_t()
+        native.check(lib.grip_prompt_couple_workspace(P, D, dt, dv, byref(nbytes)))
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        native.check(lib.grip_prompt_couple_backward(_ptr(x), _ptr(deep), P, D, dt, dv, _ptr(w), _ptr(d_prefix), _ptr(d_deep if D else None), _ptr(g_x),
+                                                     _ptr(g_deep), _ptr(g_w), _ptr(g_b), _ptr(ws), ws.numel(), _stream()))
+        return tuple(None if m is None else g.reshape(m[0]).to(m[1]) for g, m in zip((g_x, g_deep, g_w, g_b), ctx_.meta))
+
+
 def leaderboard_scan(probs, pred, path_rank, k):
     """Host scan (exact, sequential).  probs [n,c] f32 CPU, pred [n] int32 CPU, path_rank [n] int64 CPU."""
     import numpy as np

@@ -19,7 +19,7 @@ import torch
 
 from .. import clip, dist as gdist, pseudolabels as pl, steps
 from ..engine import cosine_head
-from ..models import CustomImageEncoder, CustomTextEncoder, ImagePrefixModel, TextPrefixModel, UPTModel
+from ..models import CustomImageEncoder, CustomTextEncoder, ImagePrefixModel, MaPLeModel, TextPrefixModel, UPTModel
 from ..utils import pseudolabel_top_k
 
 log = logging.getLogger(__name__)
@@ -82,6 +82,20 @@ class TrainingStrategy:
             self.vpt_init = init(1, int(c.VISION_PREFIX_SIZE), d.vision_width)
             # UPT_DEEP: vpt_embeddings_deep for blocks 1 .. layers - 1, drawn after the two prompts (which stay bit-identical with and without it)
             self.vpt_deep_init = init(d.vision_layers - 1, int(c.VISION_PREFIX_SIZE), d.vision_width) if self.upt_deep() else None
+            # MAPLE: the deep text prompts of blocks 1 .. MAPLE_DEPTH, drawn after the two prompts (which stay bit-identical with and without it);
+            # the visual side is coupled to them (MaPLeModel), so vpt_init is drawn but not trained
+            self.maple_deep_init = None
+            if self.maple():
+                if self.upt_deep():
+                    raise ValueError("MAPLE and UPT_DEEP are two different deep multimodal models: set one of them")
+                if int(c.TEXT_PREFIX_SIZE) != int(c.VISION_PREFIX_SIZE):
+                    raise ValueError(f"MAPLE couples the visual prompt to the text prompt token by token: TEXT_PREFIX_SIZE ({c.TEXT_PREFIX_SIZE}) must "
+                                     f"equal VISION_PREFIX_SIZE ({c.VISION_PREFIX_SIZE})")
+                most = min(d.transformer_layers, d.vision_layers) - 1
+                depth = int(getattr(c, "MAPLE_DEPTH", most))
+                if not 0 <= depth <= most:
+                    raise ValueError(f"MAPLE_DEPTH = {depth}: 0 .. {most} deep prompts (min(text layers, vision layers) - 1)")
+                self.maple_deep_init = init(depth, int(c.TEXT_PREFIX_SIZE), d.transformer_width) if depth else None
 
     def vpt_deep(self):
         """Deep visual prompts (VPT-Deep) for the visual strategies: config VPT_DEEP, default False.  The multimodal strategies ignore it, as the
@@ -98,6 +112,12 @@ class TrainingStrategy:
         prompts and feeds its outputs to the image tower as deep prompts."""
         return self.modality == "multi" and bool(getattr(self.config, "UPT_DEEP", False))
 
+    def maple(self):
+        """Coupled deep multimodal prompts (MaPLe) for the multimodal strategies: config MAPLE, default False (optional MAPLE_DEPTH, default
+        min(text layers, vision layers) - 1).  MaPLeModel replaces UPTModel: deep text prompts, each visual prompt a trainable Linear of the text
+        prompt of its depth.  Textual and visual strategies ignore it."""
+        return self.modality == "multi" and bool(getattr(self.config, "MAPLE", False))
+
     def define_model(self, classes=None):
         c, dev = self.config, self.device
         classes = classes if classes is not None else self.classes
@@ -109,6 +129,11 @@ class TrainingStrategy:
             deep = getattr(self, "initial_deep_prefix", None)
             self.model = ImagePrefixModel(self.initial_prefix.clone().to(dev), self.image_encoder, device=dev,
                                           deep_prefix=None if deep is None else deep.clone().to(dev))
+        elif self.maple():
+            torch.manual_seed(int(getattr(c, "OPTIM_SEED", 0)))      # the coupling Linears' initialisation
+            deep = self.maple_deep_init
+            self.model = MaPLeModel(self.coop_init.clone().to(dev), None if deep is None else deep.clone().to(dev), self.image_encoder, self.text_encoder,
+                                    classes, device=dev, dtype=torch.float32)
         else:
             torch.manual_seed(int(getattr(c, "OPTIM_SEED", 0)))
             deep = getattr(self, "vpt_deep_init", None)
@@ -140,6 +165,8 @@ class TrainingStrategy:
             return [m.prefix.detach().cpu().numpy(), m.deep_prefix.detach().cpu().numpy()]
         if self.modality in ("text", "image"):
             return [m.prefix.detach().cpu().numpy()]
+        if self.maple():      # [ctx, compound_prompts_text (None for depth 0), proj_weight, proj_bias]
+            return [None if p is None else p.detach().cpu().numpy() for p in (m.ctx, m.compound_prompts_text, m.proj_weight, m.proj_bias)]
         # multimodal_prompt.py:149-158 of the reference: the eight trainable pieces, positionally -- NOT the whole UPTModel
         # state_dict, which would drag ~1 GB of frozen CLIP weights (registered sub-modules) to the host every epoch.
         sd = lambda mod: copy.deepcopy({k: v.detach().cpu() for k, v in mod.state_dict().items()})   # noqa: E731
@@ -401,6 +428,10 @@ class TrainingStrategy:
             return text_prefix_forward(clip_model.text_tower, ids, self.model.prefix.detach(), deep=None if deep is None else deep.detach()), None
         if self.modality == "image":
             return clip_model.encode_text(clip.tokenize(self.text_prompts(classes)).to(self.device)), self.model.prefix.detach()
+        if self.maple():      # the twin's text tower reads the same deep text prompts; the image side takes vis_prefix (+ deep_prompts())
+            ctx, deep_text, vis_prefix, _ = self.model.couple()
+            ids = self.text_encoder._token_ids(ctx.shape[1], classes)
+            return text_prefix_forward(clip_model.text_tower, ids, ctx.detach(), deep=None if deep_text is None else deep_text.detach()), vis_prefix.detach()
         coop_embs, vpt_embs = self.model.mix()[:2]
         ids = self.text_encoder._token_ids(coop_embs.shape[1], classes)
         return text_prefix_forward(clip_model.text_tower, ids, coop_embs.detach()), vpt_embs.detach()
@@ -411,6 +442,8 @@ class TrainingStrategy:
         the UPT mixer's output (deep UPT; the mixer is deterministic, so this is the tensor the model's own forward feeds the tower)."""
         if self.modality == "image":
             deep = getattr(self.model, "deep_prefix", None)
+        elif self.modality == "multi" and self.maple():
+            deep = self.model.couple()[3]      # the coupled deep visual prompts
         else:
             deep = self.model.mix()[2] if self.modality == "multi" and getattr(self.model, "mix_deep", False) else None
         return None if deep is None else deep.detach()
@@ -430,6 +463,10 @@ class TrainingStrategy:
         if self.modality == "image":
             return pl.encode_pool(tower, images, chunk=chunk, prefix=self.model.prefix.detach(), deep=self.deep_prompts()), self.fixed_text_features(classes)
         self.model.classes = classes
+        if self.maple():
+            ctx, deep_text, vis_prefix, vis_deep = self.model.couple()
+            txt = self.model.text_encoder(ctx, classes, **({} if deep_text is None else {"deep_prompts": deep_text}))
+            return pl.encode_pool(tower, images, chunk=chunk, prefix=vis_prefix.detach(), deep=None if vis_deep is None else vis_deep.detach()), txt
         coop_embs, vpt_embs, *deep = self.model.mix()
         txt = self.model.text_encoder(coop_embs, classes)
         return pl.encode_pool(tower, images, chunk=chunk, prefix=vpt_embs.detach(), deep=deep[0].detach() if deep else None), txt

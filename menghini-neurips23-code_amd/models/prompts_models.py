@@ -153,3 +153,81 @@ class UPTModel(_ModuleShim, nn.Module):
         text_out = self.text_encoder(coop_embs, classes)
         visual_out = self.image_encoder(x, vpt_embs, **kw)
         return text_out, visual_out
+
+
+class MaPLeModel(_ModuleShim, nn.Module):
+    """Coupled deep multimodal prompts (MaPLe, Khattak et al., CVPR 2023): the text tower owns the prompts -- a shallow context ctx [1, P, dt] and
+    one deep context per block, compound_prompts_text [D, P, dt] -- and every visual prompt is a trainable Linear(dt -> dv) of the text prompt of
+    the same depth, with its own weights per depth: proj_weight [1 + D, dv, dt], proj_bias [1 + D, dv] (slice 0 couples ctx, slice l block l's
+    deep prompt; each initialised as nn.Linear initialises its own).  Both towers read them through the existing deep calls.  MaPLe appends its
+    visual prompts after the patch tokens, this engine inserts prompts after CLS: prompt rows carry no positional embedding and the ViT's
+    attention has no mask, so it is the same function up to f32 summation order.  Parameters and coupling arithmetic are f32 (MaPLe runs fp16;
+    its rounding points are not modelled).  compound_prompts_text None (D = 0): only the shallow pair, through the shallow tower calls.
+    forward(x, classes) -> (text_out, visual_out), un-normalised: UPTModel's contract, so steps.upt_step / GraphedUptStep serve it as they are."""
+
+    def __init__(self, ctx, compound_prompts_text, image_encoder, text_encoder, classes, temperature=0.07, device="cpu", dtype=torch.float32,
+                 vision_width=None):
+        super().__init__()
+        self.device = device
+        self.classes = classes
+        self.temperature = temperature
+        self.dtype = dtype
+        if ctx.dim() != 3 or ctx.shape[0] != 1:
+            raise ValueError(f"MaPLeModel: ctx has shape {tuple(ctx.shape)}, expected [1, P, text_width] (one shared context)")
+        self.ctx = nn.Parameter(ctx)
+        P, dt = ctx.shape[1], ctx.shape[2]
+        if compound_prompts_text is not None and (compound_prompts_text.dim() != 3 or tuple(compound_prompts_text.shape[1:]) != (P, dt)):
+            raise ValueError(f"MaPLeModel: compound_prompts_text has shape {tuple(compound_prompts_text.shape)}, expected [D, {P}, {dt}]")
+        self.compound_prompts_text = nn.Parameter(compound_prompts_text) if compound_prompts_text is not None else None
+        self.n_deep = 0 if compound_prompts_text is None else compound_prompts_text.shape[0]
+        if vision_width is None:
+            vision_width = image_encoder.visual.conv1.weight.shape[0]
+        lin = [nn.Linear(dt, int(vision_width), dtype=dtype) for _ in range(1 + self.n_deep)]      # nn.Linear's own initialisation, depth by depth
+        self.proj_weight = nn.Parameter(torch.stack([l.weight.detach() for l in lin]).to(device))
+        self.proj_bias = nn.Parameter(torch.stack([l.bias.detach() for l in lin]).to(device))
+        self.image_encoder = image_encoder
+        self.text_encoder = text_encoder
+
+    def _native_couple_ok(self):
+        """The native coupling kernel (csrc/couple.hip) covers f32 on the GPU, up to 16 prompt tokens and 31 deep sets, widths that are multiples
+        of 64 up to 1024.  Any other shape -- and GRIP_NATIVE_COUPLE=0 -- runs the same products through the framework's linear."""
+        import os
+        ts = [self.ctx, self.proj_weight, self.proj_bias] + ([] if self.compound_prompts_text is None else [self.compound_prompts_text])
+        dv, dt = self.proj_weight.shape[1], self.proj_weight.shape[2]
+        return (os.environ.get("GRIP_NATIVE_COUPLE", "1") != "0" and all(t.is_cuda and t.dtype == torch.float32 for t in ts)
+                and self.ctx.shape[1] <= 16 and self.n_deep <= 31 and dt % 64 == 0 and dv % 64 == 0 and dt <= 1024 and dv <= 1024)
+
+    def couple(self):
+        """(ctx [1, P, dt], deep_text [D, P, dt] or None, vis_prefix [P, dv], vis_deep [D, P, dv] or None): what the two towers read."""
+        deep = self.compound_prompts_text
+        if self._native_couple_ok():
+            from ..engine import PromptCoupleFn
+            out = PromptCoupleFn.apply(self.ctx, deep, self.proj_weight, self.proj_bias)
+            vis_prefix, vis_deep = (out, None) if deep is None else out
+            return self.ctx, deep, vis_prefix, vis_deep
+        linear = torch.nn.functional.linear
+        vis_prefix = linear(self.ctx[0], self.proj_weight[0], self.proj_bias[0])
+        vis_deep = None if deep is None else torch.stack([linear(deep[l], self.proj_weight[l + 1], self.proj_bias[l + 1]) for l in range(self.n_deep)])
+        return self.ctx, deep, vis_prefix, vis_deep
+
+    def forward(self, x, classes):
+        ctx, deep_text, vis_prefix, vis_deep = self.couple()
+        tkw = {} if deep_text is None else {"deep_prompts": deep_text}
+        vkw = {} if vis_deep is None else {"deep_prompts": vis_deep}
+        if x.is_cuda:
+            # the towers on two streams, as UPTModel.forward
+            main = torch.cuda.current_stream()
+            side = _side_stream(x.device)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                visual_out = self.image_encoder(x, vis_prefix, **vkw)
+            vis_prefix.record_stream(side)
+            if vis_deep is not None:
+                vis_deep.record_stream(side)
+            text_out = self.text_encoder(ctx, classes, **tkw)
+            main.wait_stream(side)
+            visual_out.record_stream(main)
+            return text_out, visual_out
+        text_out = self.text_encoder(ctx, classes, **tkw)
+        visual_out = self.image_encoder(x, vis_prefix, **vkw)
+        return text_out, visual_out

@@ -77,6 +77,11 @@ _SIGS = {
     "grip_upt_mixer_forward_deep": (c_int, [POINTER(UptMixer), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "grip_upt_mixer_backward_deep": (c_int, [POINTER(UptMixer), c_void_p, c_int, c_void_p, c_void_p, c_void_p, POINTER(UptMixer), c_void_p, c_void_p, c_size_t,
                                              c_void_p]),
+    # (ABI 9 additions) MaPLe coupling function: vis = text prompt x W[l]^T + b[l] per depth (csrc/couple.hip)
+    "grip_prompt_couple_workspace": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "grip_prompt_couple_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "grip_prompt_couple_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_size_t, c_void_p]),
     "grip_preprocess_image": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                       c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "grip_preprocess_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -61,9 +61,15 @@ def save_parameters(obj, config, iteration=None):
     """utils/compute_metrics.py:105-147 of the reference.  Textual / visual prompts: `obj` (a list holding the prompt as a
     numpy array) pickled to `{base}.pickle`.  MODALITY == "multi": `obj` is the positional list of the eight trainable pieces
     (UPT_NAMES order, methods/*/multimodal_prompt.py:149-158) and each goes to its own file -- the five state_dicts with
-    torch.save to `{base}_{name}.pt`, the three prompt arrays pickled to `{base}_{name}.pickle`.  Returns the file(s) written."""
+    torch.save to `{base}_{name}.pt`, the three prompt arrays pickled to `{base}_{name}.pickle`.  With config.MAPLE the multimodal model is
+    MaPLeModel and `obj` (ctx, compound_prompts_text, proj_weight, proj_bias) is one pickle, `{base}_maple.pickle`.  Returns the file(s) written."""
     os.makedirs("trained_prompts", exist_ok=True)
     base = _prompt_base(config, iteration)
+    if getattr(config, "MODALITY", None) == "multi" and getattr(config, "MAPLE", False):
+        # MaPLe: [ctx, compound_prompts_text, proj_weight, proj_bias] as numpy (TrainingStrategy.prompt_snapshot), one pickle
+        with open(base + "_maple.pickle", "wb") as f:
+            pickle.dump(obj, f)
+        return base + "_maple.pickle"
     if getattr(config, "MODALITY", None) == "multi":
         files = []
         for name, piece in zip(UPT_NAMES, obj):
@@ -89,6 +95,8 @@ def load_parameters(config_or_path, iteration=None):
         with open(path, "rb") as f:
             return pickle.load(f)
     base = _prompt_base(config_or_path, iteration)
+    if getattr(config_or_path, "MODALITY", None) == "multi" and getattr(config_or_path, "MAPLE", False):
+        return load_parameters(base + "_maple.pickle")
     if getattr(config_or_path, "MODALITY", None) == "multi":
         return [load_parameters(f"{base}_{n}.pt" if n in UPT_TORCH_SAVED else f"{base}_{n}.pickle") for n in UPT_NAMES]
     return load_parameters(base + ".pickle")
