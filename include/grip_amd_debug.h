@@ -63,6 +63,21 @@ int grip_debug_attention(const void* qkv, void* out, int B, int S, int H, int ca
 int grip_debug_attention_exact(const void* qkv, void* out, int B, int S, int H, int causal, void* stream);
 /* dqkv from qkv, the saved forward output o and d_out (S <= 288). */
 int grip_debug_attention_bwd(const void* qkv, const void* o, const void* d_out, void* dqkv, int B, int S, int H, int causal, void* stream);
+/* The shared-prefix row layout of the text tower (csrc/common.h seq_row; causal only): qkv and out hold shared_rows + B (S - shared_rows) rows, the first
+ * shared_rows positions once.  The backward also takes kv_part [B, shared_rows, 2, H*64] f32 (scratch: every sequence's share of the shared keys' dK / dV,
+ * summed into dqkv by attn_shared_kv_reduce_kernel). */
+int grip_debug_attention_shared(const void* qkv, void* out, int B, int S, int H, int shared_rows, void* stream);
+int grip_debug_attention_bwd_shared(const void* qkv, const void* o, const void* d_out, void* dqkv, float* kv_part, int B, int S, int H, int shared_rows,
+                                    void* stream);
+/* ONE query row per sequence (the last block of a tower): out [B, H*64] f16 from qkv [B*S, 3*H*64] f16; the query of sequence b is row row_index[b] (NULL: row 0)
+ * of the packed qkv or, qrows != NULL, row b of the compact qrows [B, H*64].  train != 0: the four-wave form (qrows must be NULL). */
+int grip_debug_attention_row(const void* qkv, const void* qrows, const int32_t* row_index, void* out, int B, int S, int H, int causal, int train, void* stream);
+/* Its backward: o_rows / do_rows [B, H*64] f16 -> the whole packed dqkv [B*S, 3*H*64] f16, zeros included. */
+int grip_debug_attention_row_bwd(const void* qkv, const void* o_rows, const void* do_rows, const int32_t* row_index, void* dqkv, int B, int S, int H, int causal,
+                                 void* stream);
+/* The one-row form of the exact / split-f16 towers: qkv and qrows (required) f32; out [B, H*64] f32 or, split_out != 0, the split layout (4 bytes per element). */
+int grip_debug_attention_row_exact(const void* qkv, const void* qrows, const int32_t* row_index, void* out, int B, int S, int H, int causal, int split_out,
+                                   void* stream);
 /* out[M,d] (f16) = LayerNorm(x[M,d] f32; gamma, beta), eps 1e-5. */
 int grip_debug_layernorm(const float* x, const float* gamma, const float* beta, void* out, int M, int d, void* stream);
 

@@ -852,6 +852,18 @@ extern "C" int grip_debug_attention_exact(const void* qkv, void* out, int B, int
 extern "C" int grip_debug_attention(const void* qkv, void* out, int B, int S, int H, int causal, void* stream) {
     return launch_attention_fwd((const half_t*)qkv, (half_t*)out, B, S, H, causal, (hipStream_t)stream);
 }
+// the shared-prefix row layout (common.h seq_row) and the one-row kernels of the last block, through the launchers the towers call
+extern "C" int grip_debug_attention_shared(const void* qkv, void* out, int B, int S, int H, int shared_rows, void* stream) {
+    return launch_attention_fwd((const half_t*)qkv, (half_t*)out, B, S, H, 1, (hipStream_t)stream, shared_rows);
+}
+extern "C" int grip_debug_attention_row(const void* qkv, const void* qrows, const int32_t* row_index, void* out, int B, int S, int H, int causal, int train,
+                                        void* stream) {
+    return launch_attention_row((const half_t*)qkv, (const half_t*)qrows, row_index, (half_t*)out, B, S, H, causal, (hipStream_t)stream, train);
+}
+extern "C" int grip_debug_attention_row_exact(const void* qkv, const void* qrows, const int32_t* row_index, void* out, int B, int S, int H, int causal,
+                                              int split_out, void* stream) {
+    return launch_attention_row_f32((const float*)qkv, (const float*)qrows, row_index, (float*)out, B, S, H, causal, (hipStream_t)stream, split_out);
+}
 extern "C" int grip_debug_layernorm(const float* x, const float* gamma, const float* beta, void* out, int M, int d, void* stream) {
     return launch_layernorm_f16_from_f32(x, gamma, beta, (half_t*)out, M, d, (hipStream_t)stream);
 }
@@ -1063,4 +1075,12 @@ extern "C" int grip_text_backward_deep(grip_tower* t, const float* grad_emb, flo
 
 extern "C" int grip_debug_attention_bwd(const void* qkv, const void* o, const void* d_out, void* dqkv, int B, int S, int H, int causal, void* stream) {
     return launch_attention_bwd((const half_t*)qkv, (const half_t*)o, (const half_t*)d_out, (half_t*)dqkv, B, S, H, causal, (hipStream_t)stream);
+}
+extern "C" int grip_debug_attention_bwd_shared(const void* qkv, const void* o, const void* d_out, void* dqkv, float* kv_part, int B, int S, int H, int shared_rows,
+                                               void* stream) {
+    return launch_attention_bwd((const half_t*)qkv, (const half_t*)o, (const half_t*)d_out, (half_t*)dqkv, B, S, H, 1, (hipStream_t)stream, shared_rows, kv_part);
+}
+extern "C" int grip_debug_attention_row_bwd(const void* qkv, const void* o_rows, const void* do_rows, const int32_t* row_index, void* dqkv, int B, int S, int H,
+                                            int causal, void* stream) {
+    return launch_attention_row_bwd((const half_t*)qkv, (const half_t*)o_rows, (const half_t*)do_rows, row_index, (half_t*)dqkv, B, S, H, causal, (hipStream_t)stream);
 }
