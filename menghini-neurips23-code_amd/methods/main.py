@@ -23,7 +23,8 @@ log = logging.getLogger(__name__)
 
 DEFAULTS = dict(MODALITY="text", PREFIX_SIZE=16, TEXT_PREFIX_SIZE=4, VISION_PREFIX_SIZE=4, TRANSFORMER_DIM=128, MEAN_INIT=0, VAR_INIT=0.02,
                 VIS_PREFIX_INIT="normal", N_LABEL=2, N_PSEUDOSHOTS=16, STEP_QUANTILE=10, BATCH_SIZE=16, EPOCHS=150, WARMUP_EPOCHS=5,
-                ACCUMULATION_ITER=1, LR=0.1, DECAY=0.1, validation_seed=0, ratio_train_val=0.8, PROMPT_TEMPLATE="a photo of a {}")
+                ACCUMULATION_ITER=1, LR=0.1, DECAY=0.1, validation_seed=0, ratio_train_val=0.8, PROMPT_TEMPLATE="a photo of a {}",
+                CACHE_POOL_FEATURES=True, POOL_CACHE_MAX_MB=8192)      # textual strategies: frozen pool embeddings kept across pseudolabel passes
 
 MODELS = {   # MODEL env value -> (strategy class, training method) -- the dispatch of methods/main_SSL.py:203-396
     "textual_prompt": (S.TextualPrompt, "train"), "visual_prompt": (S.VisualPrompt, "train"), "multimodal_prompt": (S.MultimodalPrompt, "train"),

@@ -51,6 +51,13 @@ class TrainingStrategy:
         self.val_unseen_files = self.val_unseen_labs = None
         self.balance_param = 1.0
         self.check_unlabeled = set()
+        # Textual strategies: the image tower carries no prompt and never changes, so the pool's screen embeddings and every row a refinement tower
+        # re-encoded are the same bits in every pseudolabel pass (GRIP: 10 passes over one pool): kept for the strategy's lifetime
+        # (`CACHE_POOL_FEATURES: False` restores the re-encode; POOL_CACHE_MAX_MB: the budget).  Visual and multimodal strategies encode the pool
+        # with trained prompts: they have no cache.
+        self.pool_cache = None
+        if self.modality == "text" and getattr(config, "CACHE_POOL_FEATURES", True):
+            self.pool_cache = pl.PoolFeatureCache(int(float(getattr(config, "POOL_CACHE_MAX_MB", pl.POOL_CACHE_MAX_BYTES >> 20)) * 2 ** 20))
         self.declare_custom_encoder()
         self.initialize_prompts_parameters()
 
@@ -221,8 +228,9 @@ class TrainingStrategy:
             return train_data
         c = self.config
         pseudo_classes = self.classes if self.paradigm in ("ssl", "ul") else self.unseen_classes
-        pseudolabel_top_k(c, c.DATASET_NAME, int(c.N_PSEUDOSHOTS), self.template, unlabeled_data, pseudo_classes, self.transform,
-                          self.clip_model, self.label_to_idx, self.device, c.VIS_ENCODER, getattr(c, "SPLIT_SEED", 0))
+        with pl.pool_cache(self.pool_cache):      # the frozen-CLIP pass runs the same towers over the same pool as the trained-prompt passes after it
+            pseudolabel_top_k(c, c.DATASET_NAME, int(c.N_PSEUDOSHOTS), self.template, unlabeled_data, pseudo_classes, self.transform,
+                              self.clip_model, self.label_to_idx, self.device, c.VIS_ENCODER, getattr(c, "SPLIT_SEED", 0))
         return self.merge_pseudolabels(train_data, unlabeled_data)
 
     def merge_pseudolabels(self, train_data, unlabeled_data):
@@ -449,17 +457,18 @@ class TrainingStrategy:
         return None if deep is None else deep.detach()
 
     @torch.no_grad()
-    def trained_features(self, images, classes, chunk=440):
+    def trained_features(self, images, classes, chunk=440, paths=None):
         """(image features [N, E] of the whole ordered pool, text features [C, E]) of the CURRENT model for the pseudolabel pass.
         The image side goes through pseudolabels.encode_pool: chunked, sharded contiguously over the ranks of one node, one
         all-gather of the embeddings -- with the trained visual prompt where the modality has one.  The text
         side is computed once per call on every rank (C x 6 GF, cheaper than a broadcast); the UPT mixer runs once.  The
         reference does all of this per image at batch 1 (textual_fpl.py:203-205 + :225; visual_fpl.py:250 + :264;
-        multimodal_fpl.py:223 runs BOTH towers and the mixer for every image)."""
+        multimodal_fpl.py:223 runs BOTH towers and the mixer for every image).  paths: the pool's ordered paths, the key under which a textual
+        strategy's pool cache (installed by the caller) holds the prompt-free embeddings."""
         tower = self.clip_model.visual.tower
         if self.modality == "text":
             self.model.classes = classes
-            return pl.encode_pool(tower, images, chunk=chunk), self.model(classes)
+            return pl.encode_pool(tower, images, chunk=chunk, paths=paths), self.model(classes)
         if self.modality == "image":
             return pl.encode_pool(tower, images, chunk=chunk, prefix=self.model.prefix.detach(), deep=self.deep_prompts()), self.fixed_text_features(classes)
         self.model.classes = classes
@@ -479,16 +488,18 @@ class TrainingStrategy:
         classes = self.unseen_classes if self.paradigm == "trzsl" else self.classes
         images = _pool_images(unlabeled_data, self.transform, self.device)
         labels = [self.label_to_idx[c] for c in classes]
-        if pl.mode() == "identical" and not self.clip_model.exact:
-            # the lists the reference's fp32 pass would produce with these prompts: f16 screen + exact refinement
-            twin = self.clip_model.exact_twin()
-            txt, vprompt = self.trained_text_features(classes, twin)
-            fp, lab = pl.identical_lists(self.clip_model.visual.tower, twin.visual.tower, images, txt, self.scale(),
-                                         list(unlabeled_data.filepaths), labels, k, chunk=440, prefix=vprompt, argmax_on="logits",
-                                         visual_mid=pl.mid_tower(self.clip_model, len(unlabeled_data.filepaths)), deep=self.deep_prompts())
-        else:
-            img, txt = self.trained_features(images, classes)
-            fp, lab = pl.pseudolabel_from_features(img, txt, self.scale(), list(unlabeled_data.filepaths), labels, k, argmax_on="logits")
+        paths = list(unlabeled_data.filepaths)      # the pool as passed to the pass (grip_train resets it to the original list every iteration): the cache's key
+        with pl.pool_cache(self.pool_cache):        # (None for the visual / multimodal strategies: nothing is installed)
+            if pl.mode() == "identical" and not self.clip_model.exact:
+                # the lists the reference's fp32 pass would produce with these prompts: f16 screen + exact refinement
+                twin = self.clip_model.exact_twin()
+                txt, vprompt = self.trained_text_features(classes, twin)
+                fp, lab = pl.identical_lists(self.clip_model.visual.tower, twin.visual.tower, images, txt, self.scale(),
+                                             paths, labels, k, chunk=440, prefix=vprompt, argmax_on="logits",
+                                             visual_mid=pl.mid_tower(self.clip_model, len(paths)), deep=self.deep_prompts())
+            else:
+                img, txt = self.trained_features(images, classes, paths=paths)
+                fp, lab = pl.pseudolabel_from_features(img, txt, self.scale(), paths, labels, k, argmax_on="logits")
         unlabeled_data.filepaths, unlabeled_data.labels, unlabeled_data.label_id = fp, lab, True
         return unlabeled_data
 

@@ -7,13 +7,18 @@ Two algorithmic changes against the reference loop (utils/clip_pseudolabels.py:3
 which changes a result: the class prompts are encoded once instead of once per image, and images
 go through the tower in chunks instead of one by one.
 """
+import contextlib
+import logging
 import os
+import weakref
 
 import numpy as np
 import torch
 
 from . import dist as gdist
 from . import engine
+
+log = logging.getLogger(__name__)
 
 K_ALL = 10000000   # utils/clip_pseudolabels.py:27
 
@@ -115,24 +120,227 @@ def note_screen_bound(key, stream, stats):
     stats["screen_stream_next_pass"] = _SCREEN_CHOICE[key]
 
 
+# ------------------------------------------------------------------------------------------ frozen pool features across passes
+POOL_CACHE_MAX_BYTES = 8 << 30      # per process.  A condition, not a measurement: 400 000 rows x 768 x 4 B x 3 tables ~ 3.7 GB is the largest pool a tool in the tree walks
+_PLAIN_FORMS = ("f16", "plain")     # one function of the image: the plain residual stream, chosen as a screen ("f16") or asked for as it is (screen=False: "plain")
+SCREEN_FORMS = ("hilo",) + _PLAIN_FORMS
+
+
+def screen_forms(screen):
+    """The cached stream forms an encode_pool(screen=...) request could have produced itself: the compensated stream serves only "hilo" requests; the
+    plain stream is the same bits whether a screen picked it ("f16") or a caller asked for plain embeddings (False)."""
+    return ("hilo",) if screen == "hilo" else _PLAIN_FORMS
+
+
+class _TowerEntry:
+    def __init__(self, tower):
+        self.ref = weakref.ref(tower)       # not id(): a freed tower's id can come back with other weights
+        self.screen = {}                    # stream form -> [N, E] f32 (the gathered pool embeddings, identical on every rank)
+        self.rows = self.filled = None      # refinement tier: dense [N, E] f32 table + host mask of the rows it holds
+
+    def tensors(self):
+        return list(self.screen.values()) + ([self.rows] if self.rows is not None else [])
+
+    def nbytes(self):
+        return sum(_nbytes(t) for t in self.tensors())
+
+
+def _nbytes(t):
+    return t.untyped_storage().nbytes()     # (a gathered pool is a view of its padded buffer: the buffer is what stays resident)
+
+
+class PoolFeatureCache:
+    """Embeddings of FROZEN, prompt-free image towers over ordered pools, kept on the device between pseudolabel passes.  GRIP and iterative FPL label
+    one pool every iteration (pseudo_iterative.py:62-125); with a textual strategy only the text features change between the passes, so the f16
+    screen's embeddings and every row a refinement tower has re-encoded are the same bits each time.
+
+    One entry per (pool, tower).  A pool is its ordered path tuple, compared element-wise like _RANK_CACHE (the paths NAME the images: a caller
+    that puts other images behind the same paths must clear()).  A tower is held by weak reference: the entry of a freed tower is unreachable
+    and dropped.  Calls with a visual prompt, per-image prompts or deep prompts must not come here at all (use_cache): their embeddings depend on
+    trained parameters.  Screen embeddings are kept under the stream form they were encoded in (SCREEN_FORMS) and handed out only for forms the
+    request could have produced itself; a tier entry is a dense [N, E] table and a mask of the rows written so far -- from the all-gathered rows, so
+    every rank holds the same content and computes the same miss set.
+
+    Budget: `max_bytes` over everything held (default POOL_CACHE_MAX_BYTES).  Storing evicts OTHER pools, least recently used first; an entry that
+    still does not fit is not stored (logged once) and the pass runs as it does without a cache.  Tensors handed out are the cached ones: read-only."""
+
+    def __init__(self, max_bytes=POOL_CACHE_MAX_BYTES):
+        self.max_bytes = int(max_bytes)
+        self._pools = []            # [(path tuple, [_TowerEntry])], most recently used first
+        self.hits = self.misses = 0
+        self._refused = False
+
+    # ---- lookup
+    def _find(self, paths, tower, create=False):
+        key = paths if isinstance(paths, tuple) else tuple(paths)
+        for _, towers in self._pools:           # entries of freed towers are unreachable: drop them (and a pool nothing is left of)
+            towers[:] = [t for t in towers if t.ref() is not None]
+        self._pools[:] = [p for p in self._pools if p[1]]
+        for i, (k, towers) in enumerate(self._pools):
+            if k is key or (len(k) == len(key) and k == key):      # element-wise; identical string objects compare by pointer
+                if i:
+                    self._pools.insert(0, self._pools.pop(i))
+                break
+        else:
+            if not create:
+                return None
+            towers = []
+            self._pools.insert(0, (key, towers))
+        for t in towers:
+            if t.ref() is tower:
+                return t
+        if create:
+            towers.append(_TowerEntry(tower))
+            return towers[-1]
+        return None
+
+    def _room(self, paths, need):
+        """Make room for `need` more bytes of pool `paths`: other pools go, least recently used first; False when it cannot fit."""
+        key = paths if isinstance(paths, tuple) else tuple(paths)
+        other = [i for i, (k, _) in enumerate(self._pools) if not (len(k) == len(key) and k == key)]
+        held = lambda ids: sum(t.nbytes() for i in ids for t in self._pools[i][1] if t.ref() is not None)      # noqa: E731
+        own = held(set(range(len(self._pools))) - set(other))
+        if own + need > self.max_bytes:         # not even alone: nothing is evicted for it
+            if not self._refused:
+                self._refused = True
+                log.warning("pool feature cache: %.1f MB more for a pool of %d images do not fit the budget of %.1f MB: not cached, the pass re-encodes "
+                            "as without a cache", need / 2 ** 20, len(key), self.max_bytes / 2 ** 20)
+            return False
+        while own + held(other) + need > self.max_bytes:
+            del self._pools[other.pop()]        # (indices ascend: the last is the least recently used, and deleting it moves no other)
+        return True
+
+    # ---- screen
+    def screen(self, paths, tower, forms=SCREEN_FORMS):
+        """(embeddings [N, E], form) of the pool through `tower` in one of the stream `forms`, or None."""
+        e = self._find(paths, tower)
+        for f in forms if e is not None else ():
+            if f in e.screen:
+                self.hits += 1
+                return e.screen[f], f
+        self.misses += 1
+        return None
+
+    def store_screen(self, paths, tower, form, emb):
+        """Keep the gathered [N, E] embeddings of the pool under stream form `form`.  False: over budget, not kept."""
+        if form not in SCREEN_FORMS:
+            raise ValueError(f"stream form {form!r}: expected one of {SCREEN_FORMS}")
+        e = self._find(paths, tower)
+        if e is not None and form in e.screen:
+            return True
+        if not self._room(paths, _nbytes(emb)):
+            return False
+        self._find(paths, tower, create=True).screen[form] = emb
+        return True
+
+    # ---- refinement tiers
+    def missing_rows(self, paths, tower, idx):
+        """The rows of `idx` (ascending) that `tower` has not encoded for this pool yet, ascending."""
+        idx = np.asarray(idx, dtype=np.int64)
+        e = self._find(paths, tower)
+        miss = idx if e is None or e.filled is None else idx[~e.filled[idx]]
+        if idx.size:
+            if miss.size:
+                self.misses += 1
+            else:
+                self.hits += 1
+        return miss
+
+    def filled_rows(self, paths, tower):
+        """Ascending row numbers of the pool `tower` holds embeddings of."""
+        e = self._find(paths, tower)
+        return np.empty(0, np.int64) if e is None or e.filled is None else np.flatnonzero(e.filled)
+
+    def store_rows(self, paths, tower, idx, rows, n):
+        """Write the embeddings `rows` [len(idx), E] of the pool rows `idx` (of `n`) into the tier table of `tower`.  False: the table does not fit
+        the budget and nothing was kept."""
+        idx = np.asarray(idx, dtype=np.int64)
+        e = self._find(paths, tower)
+        if e is None or e.rows is None:
+            if not self._room(paths, int(n) * rows.shape[1] * 4):
+                return False
+            e = self._find(paths, tower, create=True)
+            e.rows = torch.zeros(int(n), rows.shape[1], dtype=torch.float32, device=rows.device)
+            e.filled = np.zeros(int(n), dtype=bool)
+        if idx.size:
+            e.rows[torch.as_tensor(idx, device=e.rows.device)] = rows
+            e.filled[idx] = True
+        return True
+
+    def rows(self, paths, tower, idx):
+        """Embeddings [len(idx), E] of rows `idx`, all of which the tier table must hold."""
+        idx = np.asarray(idx, dtype=np.int64)
+        e = self._find(paths, tower)
+        if e is None or e.filled is None or not e.filled[idx].all():
+            raise KeyError("pool feature cache: rows asked for that were never stored")
+        return e.rows[torch.as_tensor(idx, device=e.rows.device)]
+
+    # ---- housekeeping
+    def clear(self):
+        self._pools.clear()
+
+    def stats(self):
+        live = [t for _, towers in self._pools for t in towers if t.ref() is not None]
+        return {"bytes": sum(t.nbytes() for t in live), "entries": len(live), "pools": len(self._pools), "hits": self.hits, "misses": self.misses,
+                "max_bytes": self.max_bytes}
+
+
+_INSTALLED = []     # caches installed by pool_cache(), innermost last.  Empty unless a caller opened one: nothing is cached by default
+
+
+@contextlib.contextmanager
+def pool_cache(cache):
+    """Install `cache` (a PoolFeatureCache, or None: no-op) for the encode_pool / identical_lists calls underneath that are not given one -- how it
+    reaches the reference-named compute_pseudo_labels / pseudolabel_top_k, whose signatures are the reference's."""
+    if cache is None:
+        yield None
+        return
+    _INSTALLED.append(cache)
+    try:
+        yield cache
+    finally:
+        _INSTALLED.pop()
+
+
+def use_cache(cache, prefix=None, deep=None):
+    """The cache a pool pass works with: the one given, else the innermost installed one, else None -- and None for every call with a visual prompt
+    (shared or per image) or deep prompts: those embeddings depend on trained parameters, the cache is neither read nor written."""
+    if prefix is not None or deep is not None:
+        return None
+    return cache if cache is not None else (_INSTALLED[-1] if _INSTALLED else None)
+
+
 @torch.no_grad()
-def encode_pool(visual_tower, images, chunk=880, prefix=None, out=None, screen=False, deep=None):
+def encode_pool(visual_tower, images, chunk=880, prefix=None, out=None, screen=False, deep=None, cache=None, paths=None):
     """Encode an ordered pool.  `images` is a tensor [N,3,R,R] (any device) or a callable
     (lo, hi) -> tensor for that slice.  With torch.distributed initialised the pool is sharded
     contiguously and the embeddings are all-gathered; returns [N, E] f32 on the device.
     screen: False, or the stream form ("hilo" / "f16") of a screen-and-refine pass's screen; True = screen_stream() without a pool history.
     prefix: None, one visual prompt for the whole pool ([P, d] / [1, P, d]), or one per image ([N, P, d], aligned with `images`: each rank
-    reads the prompts of its own shard).  deep: None or [D, P, d] deep prompts of a shared prompt (Tower.encode_chunks)."""
+    reads the prompts of its own shard).  deep: None or [D, P, d] deep prompts of a shared prompt (Tower.encode_chunks).
+    cache + paths: a PoolFeatureCache (or one installed by pool_cache) and the pool's ordered paths: a prompt-free call returns the cached embeddings
+    of a stream form this request could have produced (screen_forms) without touching `images`, and stores what it had to encode."""
     if screen is True:
         screen = screen_stream()
     n = images.shape[0] if torch.is_tensor(images) else images.n
+    cache = use_cache(cache, prefix, deep) if paths is not None else None
+    if cache is not None:
+        if len(paths) != n:
+            raise ValueError(f"{len(paths)} paths for a pool of {n} images")
+        paths = paths if isinstance(paths, tuple) else tuple(paths)
+        hit = cache.screen(paths, visual_tower, screen_forms(screen))
+        if hit is not None:
+            return hit[0]
     if engine.is_per_image_prefix(prefix) and prefix.shape[0] != n:
         raise ValueError(f"per-image visual prompts [{prefix.shape[0]}, P, d] for a pool of {n} images")
     lo, hi, per = gdist.shard_range(n)
     dev = visual_tower.device
     local = torch.empty(max(hi - lo, 0), visual_tower.embed_dim, dtype=torch.float32, device=dev)
     visual_tower.encode_chunks(images, local, lo, hi, chunk, prefix, hilo=screen == "hilo", deep=deep)
-    return gdist.allgather_rows(local, n, per, tag="pool_embeddings")
+    emb = gdist.allgather_rows(local, n, per, tag="pool_embeddings")
+    if cache is not None:
+        cache.store_screen(paths, visual_tower, screen or "plain", emb)
+    return emb
 
 
 def leaderboard(probs, pred, paths, class_labels, k):
@@ -570,20 +778,27 @@ def balanced_chunk(n_rows, chunk):
     return max(1, -(-int(n_rows) // parts))
 
 
-def tier_rows(tower, fetch, txt, scale, n, lo, hi, chunk, prefix=None, argmax_on="probs", on_rows=None, timer=None, deep=None):
+def tier_rows(tower, fetch, txt, scale, n, lo, hi, chunk, prefix=None, argmax_on="probs", on_rows=None, timer=None, deep=None, cache=None, paths=None,
+              on_cached=None):
     """A refinement tier as refine_scan's callback: rows(idx) -> (probs [len(idx), C], arg-max) of the global rows `idx` (ascending) re-encoded by `tower`.
     Each rank encodes the rows of its own shard [lo, hi) -- `fetch(global_rows)` returns their images -- and one padded all-gather assembles the rest.
     prefix: None, a shared visual prompt, or per-image prompts [n, P, d] aligned with the pool (the rows' own prompts go with them: take_prefix).
     deep: None or the shared prompt's deep prompts [D, P, d] (every row alike).
     rows.submit(idx) only ENQUEUES the work, on the tier's own HIP stream, and returns the function that waits for it: two tiers submitted back to back
-    (refine_scan does that wherever their row sets are independent) share the GPU instead of taking turns at small-batch efficiency."""
+    (refine_scan does that wherever their row sets are independent) share the GPU instead of taking turns at small-batch efficiency.
+    cache + paths (given explicitly, prompt-free tiers only): a PoolFeatureCache and the pool's path tuple.  Rows of `idx` the tower has encoded in an
+    earlier pass come from the cache; each rank encodes only the MISSING rows of its shard, one all-gather runs over the missing rows (none when
+    nothing is missing: the cache's content is the same on every rank, so every rank computes the same miss set), the head runs over the assembled
+    rows in `idx` order and the missing rows are written back.  on_rows then counts the rows actually encoded, on_cached(m) the rows served."""
     dev = tower.device
     side = torch.cuda.Stream(device=dev)
+    cache = use_cache(cache, prefix, deep) if cache is not None and paths is not None else None
 
     def submit(idx):
         import time
         t0 = time.perf_counter()
-        mine = idx[(idx >= lo) & (idx < hi)]
+        need = idx if cache is None else cache.missing_rows(paths, tower, idx)
+        mine = need[(need >= lo) & (need < hi)]
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             local = torch.empty(len(mine), tower.embed_dim, dtype=torch.float32, device=dev)
@@ -592,7 +807,16 @@ def tier_rows(tower, fetch, txt, scale, n, lo, hi, chunk, prefix=None, argmax_on
                                     streams=tier_streams(), deep=deep)
             if on_rows is not None:
                 on_rows(len(mine))
-            got = gdist.allgather_selected(local, idx, n, tag="refined_rows")
+            if cache is None:
+                got = gdist.allgather_selected(local, idx, n, tag="refined_rows")
+            else:
+                if on_cached is not None:
+                    on_cached(len(idx) - len(need))
+                got = gdist.allgather_selected(local, need, n, tag="refined_rows") if len(need) else local
+                # the table is written and read on this tier's stream only, and every submit is waited for (result) before the pass ends: a later
+                # pass's stream starts behind it.  A table over budget is never created: nothing was cached then, `need` is `idx`, `got` is complete
+                if cache.store_rows(paths, tower, need, got, n):
+                    got = cache.rows(paths, tower, idx)
             _, p, al, ap = engine.cosine_head(got, txt, scale)
             am = ap if argmax_on == "probs" else al
         if timer is not None:
@@ -615,7 +839,7 @@ def tier_rows(tower, fetch, txt, scale, n, lo, hi, chunk, prefix=None, argmax_on
 
 @torch.no_grad()
 def identical_lists(visual16, visual32, images, txt_exact, scale, paths, class_labels, k, chunk=880, exact_chunk=880, prefix=None,
-                    argmax_on="probs", streams=2, emb16=None, visual_mid=None, mid_chunk=880, deep=None):
+                    argmax_on="probs", streams=2, emb16=None, visual_mid=None, mid_chunk=880, deep=None, cache=None):
     """(filepaths, labels) of the reference's fp32 pseudolabel scan (utils/clip_pseudolabels.py:24-112) at close to the f16
     towers' throughput: the whole pool goes through the f16 vision tower `visual16` (sharded over ranks, one all-gather), the
     head scores it against the EXACT text features `txt_exact`, and refine_scan re-encodes only the rows whose probabilities cannot
@@ -625,34 +849,53 @@ def identical_lists(visual16, visual32, images, txt_exact, scale, paths, class_l
     was left at; the bound is calibrated on this pool, audited on a hold-out sample after certification and reported in
     LAST_REFINE_STATS (asserted equal to the exact mode at N = 50 000 in tests/test_gpu_identical.py).  prefix: None, one visual prompt for
     the pool, or one per image ([N, P, d]): every tier encodes a row with its own prompt.  deep: None or [D, P, d] deep prompts of a shared
-    prompt, given to the screen and to every tier alike."""
+    prompt, given to the screen and to every tier alike.
+    cache: a PoolFeatureCache (or one installed by pool_cache) for prompt-free passes: the screen's embeddings come from it when it holds them in
+    ANY stream form (the lists do not depend on the screen's stream; `images` is then never read for the screen and nothing is gathered), and every
+    tier re-encodes only rows it has not encoded in an earlier pass over these `paths` (tier_rows).  refine_scan asks for the same rows and gets the
+    same bits either way: lists, marks and bounds are those of the uncached pass.  LAST_REFINE_STATS: `screen_cached`, `rows_cached_mid` /
+    `rows_cached_exact` (rows the tiers were asked for and did not encode); rows_*_this_rank count rows actually encoded."""
     global LAST_REFINE_STATS
     n = len(paths)
     if n == 0:
         _, _, LAST_REFINE_STATS = refine_scan(np.empty((0, max(len(class_labels), 1)), np.float32), np.empty(0, np.int32), np.empty(0, np.int64), k, None)
-        LAST_REFINE_STATS["rows_refined_this_rank"] = 0
+        LAST_REFINE_STATS.update(rows_refined_this_rank=0, rows_cached_mid=0, rows_cached_exact=0, screen_cached=False)
         return [], []
+    cache = use_cache(cache, prefix, deep)
+    pool = tuple(paths) if cache is not None else None
     key = (id(visual16), n, len(class_labels))        # the pool as far as the screen's choice of stream goes (same tower, same size, same class count)
-    stream = screen_stream(key) if emb16 is None else None
-    emb = emb16 if emb16 is not None else encode_pool(visual16, images, chunk=chunk, prefix=prefix, screen=stream, deep=deep)
+    hit = cache.screen(pool, visual16) if cache is not None and emb16 is None else None
+    stream = screen_stream(key) if emb16 is None and hit is None else None       # (a cached screen, like a given one, makes no stream choice)
+    if hit is not None:
+        emb = hit[0]
+    else:
+        emb = emb16 if emb16 is not None else encode_pool(visual16, images, chunk=chunk, prefix=prefix, screen=stream, deep=deep, cache=cache, paths=pool)
     dev = emb.device
     _, probs, am_l, am_p = engine.cosine_head(emb, txt_exact, scale)
     probs_h = probs.cpu().numpy()
     pred_h = (am_p if argmax_on == "probs" else am_l).cpu().numpy()
     lo, hi, _ = gdist.shard_range(n)
     encoded = {"exact": 0, "mid": 0}
+    served = {"exact": 0, "mid": 0}
 
     def rows_through(tower, tier, tier_chunk):
         def count(m):
             encoded[tier] += m
-        return tier_rows(tower, lambda rows: take_images(images, rows), txt_exact, scale, n, lo, hi, tier_chunk, prefix, argmax_on, on_rows=count, deep=deep)
+
+        def count_cached(m):
+            served[tier] += m
+        return tier_rows(tower, lambda rows: take_images(images, rows), txt_exact, scale, n, lo, hi, tier_chunk, prefix, argmax_on, on_rows=count, deep=deep,
+                         cache=cache, paths=pool, on_cached=count_cached)
 
     img, cls, stats = refine_scan(probs_h, pred_h, path_ranks(paths), k, rows_through(visual32, "exact", exact_chunk),
                                   mid_rows=rows_through(visual_mid, "mid", mid_chunk) if visual_mid is not None else None)
     stats["rows_refined_this_rank"] = encoded["exact"] + encoded["mid"]
     stats["rows_exact_this_rank"], stats["rows_mid_this_rank"] = encoded["exact"], encoded["mid"]
+    stats["rows_cached_exact"], stats["rows_cached_mid"], stats["screen_cached"] = served["exact"], served["mid"], hit is not None
     if stream is not None:
         note_screen_bound(key, stream, stats)
+    elif hit is not None:
+        stats["screen_stream"] = hit[1]           # the form the cached screen was encoded in
     LAST_REFINE_STATS = stats
     return [paths[i] for i in img], [class_labels[int(c)] for c in cls]
 

@@ -88,7 +88,7 @@ def compute_pseudo_labels(k, template, dataset, classnames, transform, clip_mode
     else:
         with torch.no_grad():
             txt = clip_model.encode_text(text)                                 # once, not once per image
-            emb = pl.encode_pool(clip_model.visual.tower, images, chunk=chunk)
+            emb = pl.encode_pool(clip_model.visual.tower, images, chunk=chunk, paths=list(dataset.filepaths))     # (the paths key a cache installed by pl.pool_cache)
         new_imgs, new_labels = pl.pseudolabel_from_features(emb, txt, scale, list(dataset.filepaths), class_labels, k, argmax_on="probs")
     dataset.filepaths = new_imgs
     dataset.labels = new_labels
