@@ -300,6 +300,27 @@ int grip_prompt_couple_backward(const float* ctx, const float* deep_text, int n_
                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 9 additions) Key/value cache head (Tip-Adapter; models/cache_models.py TipAdapterModel; csrc/cache_head.hip).  All tensors f32 on the device,
+ * img_emb / keys / grad_keys 16-byte aligned.
+ *   img_emb      [n, e]     image embeddings, NOT normalised (as grip_cosine_head takes them); f^_i = f_i / |f_i| is folded into the score
+ *   keys         [m, e]     the cache keys, grouped by class and used as stored (not renormalised)
+ *   class_start  [c + 1]    int32, device: class y owns the key rows class_start[y] .. class_start[y + 1] - 1; class_start[0] = 0, class_start[c] = m,
+ *                           non-decreasing (the caller's duty: it is device data); a class may own no key
+ *   key_weight   [m]        v_j, or NULL for 1
+ *   forward:  logits_inout[i, y] += alpha * sum_{j in class y} v_j exp(-beta (1 - f^_i . k_j)); the column of a class without keys is not written
+ *   backward: grad_keys[j, d] = alpha beta v_j sum_i grad_logits[i, y(j)] exp(-beta (1 - f^_i . k_j)) f^_id -- written, not accumulated; it recomputes
+ *             the affinities and needs no forward before it.  (No gradient to img_emb: the image tower of the strategies that use the head is frozen.)
+ *   e a multiple of 4 up to 2048; n, m, c >= 1, any c.  The products run on the f32 MFMA; the [n, m] affinities never reach memory; no atomics, one
+ *   writer per element, fixed summation order: bit-reproducible, and the bits of a row do not depend on n or on the call the row is in.
+ *   workspace: grip_cache_head_workspace bytes (the reciprocal row norms), scratch of either call. */
+int grip_cache_head_workspace(int n, int m, int c, int e, size_t* bytes);
+int grip_cache_head_forward(const float* img_emb, const float* keys, const int32_t* class_start, const float* key_weight, float alpha, float beta,
+                            int n, int m, int c, int e, float* logits_inout, void* workspace, size_t workspace_bytes, void* stream);
+int grip_cache_head_backward(const float* img_emb, const float* keys, const int32_t* class_start, const float* key_weight, float alpha, float beta,
+                             int n, int m, int c, int e, const float* grad_logits, float* grad_keys, void* workspace, size_t workspace_bytes,
+                             void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CLIP preprocessing of one decoded image: the `_transform` the reference applies per item on the host
  * (data/dataset.py:64-79 via clip.load's preprocess): Resize(n_px, BICUBIC) -> CenterCrop(n_px) -> ToTensor -> Normalize.
  * Bit-exact with Pillow's 8-bit bicubic resample; only the cropped rows / columns are produced.

@@ -705,6 +705,69 @@ class PromptCoupleFn(torch.autograd.Function):
         return tuple(None if m is None else g.reshape(m[0]).to(m[1]) for g, m in zip((g_x, g_deep, g_w, g_b), ctx_.meta))
 
 
+def _cache_head_args(img_emb, keys, class_start, key_weight, logits):
+    """Contiguous f32 / int32 operands and (n, m, c, e) of a cache-head call, shapes checked (the values of class_start are the caller's:
+    models.cache_models.TipAdapterModel builds and validates them on the host)."""
+    img, k = img_emb.detach().contiguous().float(), keys.detach().contiguous().float()
+    cs = class_start.to(device=img.device, dtype=torch.int32).contiguous()
+    v = None if key_weight is None else key_weight.detach().to(device=img.device, dtype=torch.float32).contiguous()
+    if img.dim() != 2 or k.dim() != 2 or logits.dim() != 2 or k.shape[1] != img.shape[1] or logits.shape[0] != img.shape[0] \
+            or cs.dim() != 1 or cs.numel() != logits.shape[1] + 1 or (v is not None and tuple(v.shape) != (k.shape[0],)):
+        raise native.GripError(f"cache head: img_emb {tuple(img_emb.shape)}, keys {tuple(keys.shape)}, class_start {tuple(class_start.shape)}, key_weight "
+                               f"{None if key_weight is None else tuple(key_weight.shape)}, logits {tuple(logits.shape)}: expected [n, e], [m, e], [c + 1], "
+                               "[m], [n, c]")
+    return img, k, cs, v, (img.shape[0], k.shape[0], logits.shape[1], img.shape[1])
+
+
+def _cache_head_workspace(dims, device):
+    nbytes = c_size_t()
+    native.check(native.lib().grip_cache_head_workspace(*dims, byref(nbytes)))
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+
+def cache_head(img_emb, keys, class_start, key_weight, alpha, beta, clip_logits):
+    """Tip-Adapter's cache term added to a CLONE of clip_logits [n, c] on the native kernel (csrc/cache_head.hip), no autograd:
+    out[i, y] = clip_logits[i, y] + alpha * sum_{j in class y} key_weight[j] * exp(-beta * (1 - normalize(img_emb)[i] . keys[j]))."""
+    out = clip_logits.detach().float().clone(memory_format=torch.contiguous_format)
+    img, k, cs, v, dims = _cache_head_args(img_emb, keys, class_start, key_weight, out)
+    ws = _cache_head_workspace(dims, img.device)
+    native.check(native.lib().grip_cache_head_forward(_ptr(img), _ptr(k), _ptr(cs), _ptr(v), float(alpha), float(beta), *dims, _ptr(out), _ptr(ws), ws.numel(),
+                                                      _stream()))
+    return out
+
+
+class CacheHeadFn(torch.autograd.Function):
+    """(img_emb, keys, class_start, key_weight or None, alpha, beta, clip_logits) -> adapted logits, native forward and backward.  The gradient goes to
+    the keys (Tip-Adapter-F trains them alone) and, unchanged, to clip_logits; the image embeddings come from a frozen tower and get none --
+    marking them as requiring grad is an error, not a silent zero."""
+
+    @staticmethod
+    def forward(ctx, img_emb, keys, class_start, key_weight, alpha, beta, clip_logits):
+        if img_emb.requires_grad:
+            raise native.GripError("cache head: img_emb requires grad, but the head has no gradient for the image embeddings (its image tower is frozen); "
+                                   "detach them")
+        out = cache_head(img_emb, keys, class_start, key_weight, alpha, beta, clip_logits)
+        ctx.save_for_backward(img_emb.detach(), keys.detach(), class_start, *([] if key_weight is None else [key_weight.detach()]))
+        ctx.hyper = (float(alpha), float(beta))
+        ctx.meta = (keys.shape, keys.dtype, clip_logits.dtype, keys.requires_grad, clip_logits.requires_grad)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        img, keys, cs, *rest = ctx.saved_tensors
+        shape, dtype, ldtype, need_k, need_l = ctx.meta
+        g = grad_out.contiguous().float()
+        gk = None
+        if need_k:
+            img, k, cs, v, dims = _cache_head_args(img, keys, cs, rest[0] if rest else None, g)
+            gk = torch.empty_like(k)
+            ws = _cache_head_workspace(dims, img.device)
+            native.check(native.lib().grip_cache_head_backward(_ptr(img), _ptr(k), _ptr(cs), _ptr(v), *ctx.hyper, *dims, _ptr(g), _ptr(gk), _ptr(ws),
+                                                               ws.numel(), _stream()))
+            gk = gk.reshape(shape).to(dtype)
+        return None, gk, None, None, None, None, (grad_out.to(ldtype) if need_l else None)
+
+
 def leaderboard_scan(probs, pred, path_rank, k):
     """Host scan (exact, sequential).  probs [n,c] f32 CPU, pred [n] int32 CPU, path_rank [n] int64 CPU."""
     import numpy as np

@@ -19,7 +19,7 @@ import torch
 
 from .. import clip, dist as gdist, pseudolabels as pl, steps
 from ..engine import cosine_head
-from ..models import CustomImageEncoder, CustomTextEncoder, ImagePrefixModel, MaPLeModel, TextPrefixModel, UPTModel
+from ..models import CustomImageEncoder, CustomTextEncoder, ImagePrefixModel, MaPLeModel, TextPrefixModel, TipAdapterModel, UPTModel
 from ..utils import pseudolabel_top_k
 
 log = logging.getLogger(__name__)
@@ -58,6 +58,10 @@ class TrainingStrategy:
         self.pool_cache = None
         if self.modality == "text" and getattr(config, "CACHE_POOL_FEATURES", True):
             self.pool_cache = pl.PoolFeatureCache(int(float(getattr(config, "POOL_CACHE_MAX_MB", pl.POOL_CACHE_MAX_BYTES >> 20)) * 2 ** 20))
+        # TIP_ADAPTER (textual strategies): the key/value cache built from the training set after each prompt training (build_tip_cache); None = off
+        self.tip, self.tip_classes, self.tip_losses, self.tip_search = None, None, [], None
+        if bool(getattr(config, "TIP_ADAPTER", False)) and self.modality != "text":
+            log.info(f"TIP_ADAPTER is ignored by the {self.modality} strategies: their pool features move with the prompt (textual strategies only)")
         self.declare_custom_encoder()
         self.initialize_prompts_parameters()
 
@@ -125,8 +129,15 @@ class TrainingStrategy:
         prompt of its depth.  Textual and visual strategies ignore it."""
         return self.modality == "multi" and bool(getattr(self.config, "MAPLE", False))
 
+    def tip_adapter(self):
+        """Tip-Adapter cache head for the textual strategies: config TIP_ADAPTER, default False (TIP_ALPHA 1.0, TIP_BETA 5.5, TIP_PSEUDO_WEIGHT 1.0,
+        TIP_FINETUNE_EPOCHS 0 = training-free, TIP_LR 1e-3, TIP_SEARCH False).  Their image tower is frozen and their training features are cached, so
+        the cache costs no tower pass.  Visual and multimodal strategies ignore it, as they ignore COOP_DEEP."""
+        return self.modality == "text" and bool(getattr(self.config, "TIP_ADAPTER", False))
+
     def define_model(self, classes=None):
         c, dev = self.config, self.device
+        self.tip = None      # a cache belongs to the prompt it was built after: validation during the next training sees CLIP logits alone
         classes = classes if classes is not None else self.classes
         if self.modality == "text":
             deep = getattr(self, "initial_deep_prefix", None)
@@ -385,6 +396,8 @@ class TrainingStrategy:
             img = batch[0].to(self.device)
             image_features, text_features = self.features(img, classes)
             logits, _, am, _ = cosine_head(image_features, text_features, self.scale(), want_probs=False)
+            if self.tip is not None:      # TIP_ADAPTER: the cache term of the iteration's training set
+                logits = self._add_cache_term(image_features, logits, classes)
             outs.append(logits)
         logits = torch.cat(outs) if outs else torch.empty(0, len(classes), device=self.device)
         logits = gdist.gather_in_dataset_order(logits, len(data), int(self.config.BATCH_SIZE))
@@ -407,7 +420,91 @@ class TrainingStrategy:
             log.info(f"epoch {epoch}: loss {loss:.4f} train acc {acc:.3f} val acc {val_acc:.3f}")
             if val_acc > best_acc:
                 best_acc, best_prompt = val_acc, self.prompt_snapshot()
+        if self.tip_adapter():
+            self.build_tip_cache(train_data, val_data, only_seen=only_seen)
         return best_acc, best_prompt
+
+    # ------------------------------------------------------------------ Tip-Adapter cache (TIP_ADAPTER, textual strategies)
+    @torch.no_grad()
+    def _tip_inputs(self, data, classes, lut):
+        """(frozen image features [N, E], CLIP logits [N, C] of the current prompt, class positions [N], names) of a labelled dataset, in dataset
+        order; items whose label is outside `classes` are dropped."""
+        feats, labs, names = [], [], []
+        for img, _, _, label, nm in torch.utils.data.DataLoader(data, batch_size=int(self.config.BATCH_SIZE), shuffle=False):
+            feats.append(self.frozen_image_features(img.to(self.device), list(nm)))
+            label = label.to(self.device)
+            labs.append(torch.where(label < len(lut), lut[label.clamp(max=len(lut) - 1)], torch.full_like(label, -1)))
+            names += list(nm)
+        feats, labs = torch.cat(feats), torch.cat(labs)
+        keep = labs >= 0
+        self.model.classes = classes
+        logits = cosine_head(feats[keep], self.model(classes), self.scale(), want_probs=False)[0]
+        return feats[keep], logits, labs[keep], [n for n, k in zip(names, keep.tolist()) if k]
+
+    def build_tip_cache(self, train_data, val_data=None, only_seen=False):
+        """The Tip-Adapter cache of the iteration just trained: keys = the unit-normalised frozen features of the training set (labelled shots and
+        pseudolabelled pool rows: the same cached embeddings the prompt steps read), values = their labels, key weight TIP_PSEUDO_WEIGHT for the
+        pseudolabelled rows.  TIP_FINETUNE_EPOCHS > 0 trains the keys alone (Tip-Adapter-F: steps.GraphedTipStep on the training set, AdamW at TIP_LR);
+        TIP_SEARCH picks (alpha, beta) on the validation set.  From here on predict() -- hence _run_validation, test_predictions and evaluation -- adds
+        the cache term to the logits it computes.
+
+        The pseudolabel pass is NOT touched: assign_pseudo_labels and the frozen-CLIP pass keep ranking the pool by the CLIP logits of the prompts
+        alone, so their lists stay the certified lists of the reference function."""
+        c = self.config
+        classes, ids, lut = self._class_space(only_seen)
+        feats, clip_logits, labs, names = self._tip_inputs(train_data, classes, lut)
+        pseudo = [getattr(self, "fpl", False) and (self.paradigm == "ul" or n in self.check_unlabeled) for n in names]
+        epochs = int(getattr(c, "TIP_FINETUNE_EPOCHS", 0))
+        self.tip = TipAdapterModel.from_lists(feats, labs, pseudo, len(classes), pseudo_weight=float(getattr(c, "TIP_PSEUDO_WEIGHT", 1.0)),
+                                              alpha=float(getattr(c, "TIP_ALPHA", 1.0)), beta=float(getattr(c, "TIP_BETA", 5.5)), train_keys=epochs > 0)
+        self.tip_classes, self.tip_losses, self.tip_search = list(classes), [], None
+        if epochs > 0:
+            B = int(c.BATCH_SIZE)
+            opt = torch.optim.AdamW([self.tip.keys], lr=float(getattr(c, "TIP_LR", 1e-3)), eps=1e-4)
+            step = steps.GraphedTipStep(self.tip, opt) if getattr(c, "GRAPH_STEPS", True) else None
+            g = torch.Generator().manual_seed(int(getattr(c, "LOADER_SEED", 0)))
+            gid = ids[labs].tolist()      # global label ids, as row_weights reads them
+            for _ in range(epochs):
+                order = torch.randperm(len(names), generator=g).tolist()
+                total, nb = torch.zeros((), dtype=torch.float64, device=self.device), 0
+                for lo in range(0, len(order), B):
+                    rows = order[lo:lo + B]
+                    idx = torch.tensor(rows, device=self.device)
+                    w = self.row_weights([gid[r] for r in rows], [names[r] for r in rows]).to(self.device)
+                    if step is not None:
+                        total += step(feats[idx], labs[idx], w, clip_logits[idx])
+                    else:
+                        total += steps.tip_step(self.tip, feats[idx], clip_logits[idx], labs[idx].to(torch.int32), w, opt)
+                    nb += 1
+                self.tip_losses.append(float(total) / max(nb, 1))
+            log.info(f"Tip-Adapter-F: {epochs} epochs over {len(names)} keys, loss {self.tip_losses[0]:.4f} -> {self.tip_losses[-1]:.4f}")
+        if bool(getattr(c, "TIP_SEARCH", False)) and val_data is not None and len(val_data):
+            vf, vl, vy, _ = self._tip_inputs(val_data, classes, lut)
+            if len(vy):
+                self.tip_search = self.tip.search(list(getattr(c, "TIP_ALPHA_GRID", (0.5, 1.0, 2.0, 3.0, 5.0))),
+                                                  list(getattr(c, "TIP_BETA_GRID", (1.0, 3.0, 5.5, 8.0))), vf, vl, vy)
+                log.info(f"Tip-Adapter search: alpha {self.tip_search[0]:g} beta {self.tip_search[1]:g} (validation accuracy {self.tip_search[2]:.3f})")
+        return self.tip
+
+    def load_tip_cache(self, path, classes=None):
+        """Install a cache file written by utils.save_parameters(..., cache=strategy.tip); `classes`: its class list (default: all classes)."""
+        self.tip = TipAdapterModel.load(path, device=self.device)
+        self.tip_classes = list(classes if classes is not None else self.classes)
+        return self.tip
+
+    @torch.no_grad()
+    def _add_cache_term(self, image_features, logits, classes):
+        """logits [N, len(classes)] + the cache term of the columns the cache knows (all of them when `classes` is the cache's own list: then the
+        kernel adds in place of a clone; otherwise the term is computed against zeros and its columns are gathered)."""
+        if list(classes) == self.tip_classes:
+            return self.tip(image_features, logits)
+        term = self.tip(image_features, torch.zeros(logits.shape[0], len(self.tip_classes), device=logits.device))
+        pos = {c: i for i, c in enumerate(self.tip_classes)}
+        cols = [(j, pos[c]) for j, c in enumerate(classes) if c in pos]
+        if cols:
+            dst, src = (torch.tensor(x, device=logits.device) for x in zip(*cols))
+            logits[:, dst] += term[:, src]
+        return logits
 
     # ------------------------------------------------------------------ evaluation
     def test_predictions(self, data, standard_zsl=False):
@@ -533,7 +630,7 @@ class TrainingStrategy:
             out = self.train(data, val_data, only_seen=only_seen, iter_train=True)
             from ..utils import save_parameters, save_pseudo_labels
             save_pseudo_labels(list(data.filepaths), list(data.labels), c, niter)     # compute_metrics.py:150-154
-            save_parameters(out[1], c, iteration=niter)
+            save_parameters(out[1], c, iteration=niter, cache=self.tip)
             log.info(f"GRIP iteration {niter}/{num_iter}: {c.N_PSEUDOSHOTS} pseudo-shots per class, val acc {out[0]:.3f}")
         return out
 

@@ -360,3 +360,41 @@ class GraphedUptStep(GraphedStep):
 
     def eager(self, images, labels, row_weight):
         return upt_step(self.model, self.scale, images, labels, row_weight, self.optimizer, return_logits=True)
+
+
+def tip_step(model, image_features, clip_logits, labels, row_weight, optimizer, return_logits=False):
+    """Tip-Adapter-F step on a models.TipAdapterModel with train_keys: cache head over cached image features and the CLIP logits of the trained
+    prompt (both constants of the step) -> weighted CE -> the keys' gradient -> optimizer.  No tower runs."""
+    logits = model(image_features, clip_logits)
+    loss = WeightedCEFn.apply(logits, labels, row_weight)
+    return _finish(loss, [model.keys], optimizer, logits if return_logits else None)
+
+
+class GraphedTipStep(GraphedStep):
+    """tip_step replayed from a HIP graph: the cache head's forward and backward and the loss are four kernels, so a step is launch cost and little
+    else.  The static inputs are the feature block [B, embed_dim] (GraphedStep's `x`) and the CLIP logits [B, C] of the same rows; call it as
+    step(image_features, labels, row_weight, clip_logits)."""
+
+    def __init__(self, model, optimizer):
+        super().__init__(optimizer)
+        self.model = model
+        self.z = None
+
+    def params(self):
+        return [self.model.keys]
+
+    def forward_logits(self):
+        return self.model(self.x, self.z)
+
+    def eager(self, feats, labels, row_weight):
+        return tip_step(self.model, feats, self._clip_logits, labels, row_weight, self.optimizer, return_logits=True)
+
+    def __call__(self, feats, labels, row_weight, clip_logits):
+        self._clip_logits = clip_logits
+        if self.z is None or self.z.shape != clip_logits.shape:
+            if self.graph is not None:      # another batch shape: the eager step (GraphedStep.__call__ sees the feature block's shape differ too)
+                return super().__call__(feats, labels, row_weight)
+            self.z = clip_logits.detach().float().clone()
+        else:
+            self.z.copy_(clip_logits)
+        return super().__call__(feats, labels, row_weight)
