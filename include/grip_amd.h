@@ -356,6 +356,25 @@ int grip_preprocess_batch(const grip_preprocess_item* items_device, int n_items,
                           const float* mean3, const float* std3, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 9 addition) Train-time views of the f32 pool (RandomResizedCrop + RandomHorizontalFlip; csrc/augment.hip; the `augmentations` slot of the
+ * reference's datasets, data/dataset.py:18-79).  View v crops the box [top, top + height) x [left, left + width) of image `row`, resamples it to
+ * n_px x n_px with Pillow's antialiased bicubic (a = -0.5: precompute_coeffs applied to the BOX, i.e. crop() followed by resize() -- taps clip at the
+ * box edge and nothing outside the box is read) and, when `flip` is non-zero, mirrors the result left-right.
+ *   src            [n_src, 3, H, W] f32, contiguous, device
+ *   views_device   DEVICE array of n_views descriptors; 0 <= row < n_src, 1 <= height <= H - top, 1 <= width <= W - left, top, left >= 0.  The caller
+ *                  validates them (grip_amd.augment.views does, on the host); a descriptor outside the pool writes nothing.
+ *   out            [n_views, 3, n_px, n_px] f32 device; any n_px >= 1 (16-byte stores when n_px % 4 == 0 and out is 16-byte aligned)
+ * Weights are evaluated and normalised in float64 on the device and rounded to f32 once; both passes accumulate in f32.  A box with
+ * height == width == n_px and no flip is a bit-exact copy.  No allocation, no synchronisation, no atomics; a view's bits depend on its own descriptor
+ * only (not on n_views, its position in the launch or the other views).  Element offsets are 64-bit. */
+typedef struct {
+    int64_t row;
+    int32_t top, left, height, width, flip, pad;
+} grip_view;
+int grip_augment_views(const float* src, int64_t n_src, int H, int W, const grip_view* views_device, int64_t n_views, int n_px,
+                       float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Sequential per-class leaderboard: utils/clip_pseudolabels.py:49-112 and the nine
  * assign_pseudo_labels (e.g. methods/transductive_zsl/multimodal_fpl.py:194-285).  Host function,
  * exact: order-dependent, one pass in dataset order.

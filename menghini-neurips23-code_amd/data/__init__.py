@@ -16,7 +16,7 @@ class ImagePool:
 
 
 class TensorPoolDataset(Dataset):
-    def __init__(self, filepaths, images, root="", train=True, labels=None, label_id=False, label_map=None, transform=None):
+    def __init__(self, filepaths, images, root="", train=True, labels=None, label_id=False, label_map=None, transform=None, augmentations=None):
         sub = "train" if train else "test"
         self.filepaths = [f"{root}/{sub}/{f}" if root else f for f in filepaths]
         if isinstance(images, ImagePool):
@@ -29,6 +29,21 @@ class TensorPoolDataset(Dataset):
         self.label_id = label_id
         self.label_map = label_map
         self.train = train
+        # the reference's `augmentations=(aug1, aug2)` slot (data/dataset.py:18-79): a pair of grip_amd.augment.ViewSampler (or None per slot);
+        # an item's aug_1 / aug_2 are views 0 / 1 of the image under its basename and `epoch`, the function ViewSampler.batch applies to a batch
+        self.augmentations = (None, None) if augmentations is None else tuple(augmentations)
+        if len(self.augmentations) != 2:
+            raise ValueError("augmentations: a pair (aug1, aug2) of ViewSampler or None")
+        self.epoch = 0
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def _view(self, k, img, name):
+        aug = self.augmentations[k]
+        if aug is None:
+            return img
+        return aug.batch(img[None].contiguous().cuda(), [name], self.epoch, view=k)[0]
 
     @property
     def images(self):
@@ -49,5 +64,5 @@ class TensorPoolDataset(Dataset):
         name = path.split("/")[-1]
         if self.labels is not None:
             label = int(self.labels[index]) if self.label_id else int(self.label_map[self.labels[index]])
-            return img, img, img, label, name
-        return img, img, img, name
+            return img, self._view(0, img, name), self._view(1, img, name), label, name
+        return img, self._view(0, img, name), self._view(1, img, name), name

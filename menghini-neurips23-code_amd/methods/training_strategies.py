@@ -318,21 +318,41 @@ class TrainingStrategy:
             self._gkey, self._gstep = key, g
         return self._gstep
 
-    def _train_epoch(self, train_loader, only_seen=False):
+    def view_sampler(self):
+        """The train-time augmentation of the prompt steps (config AUGMENT, default False; "rrc_flip" = RandomResizedCrop + RandomHorizontalFlip, the
+        training transform CoOp, VPT, MaPLe and Tip-Adapter-F are published with): a grip_amd.augment.ViewSampler with AUG_SCALE (0.08, 1.0),
+        AUG_RATIO (3/4, 4/3), AUG_FLIP 0.5 and AUG_SEED 0, or None.  Only the batches of `_train_epoch` are augmented: validation, predict, evaluation,
+        the Tip-Adapter cache build and every pseudolabel pass read the pool as it is."""
+        c = self.config
+        mode = getattr(c, "AUGMENT", False)
+        if not mode:
+            return None
+        if mode != "rrc_flip":
+            raise ValueError(f"AUGMENT: {mode!r} is not a known augmentation (False or 'rrc_flip')")
+        from ..augment import ViewSampler
+        return ViewSampler(seed=int(getattr(c, "AUG_SEED", 0)), scale=tuple(getattr(c, "AUG_SCALE", (0.08, 1.0))),
+                           ratio=tuple(getattr(c, "AUG_RATIO", (3.0 / 4.0, 4.0 / 3.0))), flip=float(getattr(c, "AUG_FLIP", 0.5)))
+
+    def _train_epoch(self, train_loader, only_seen=False, epoch=0):
         """One epoch of the strategy's prompt step (the `_train_epoch` bodies of the reference, e.g. textual_prompt.py:63-159).
         Default: every full-sized batch replays the step's forward + backward from a HIP graph (steps.Graphed*Step; a batch of
         another shape -- the ragged last one -- runs the same kernels eagerly), the textual modality encodes the frozen image
         tower `IMAGE_LOOKAHEAD` (51) batches at a time when its features are not cached, and loss / accuracy accumulate on the
         device: one host synchronisation per epoch instead of three per batch.  `GRAPH_STEPS: False` or gradient accumulation
-        (ACCUMULATION_ITER > 1) take the eager per-batch path."""
+        (ACCUMULATION_ITER > 1) take the eager per-batch path.
+
+        With AUGMENT on, every batch's `img` (what the reference trains on) is replaced on the device by its view of `epoch` (view_sampler: one
+        launch per batch, outside the graph -- the graphed steps copy their batch into a static buffer).  The frozen features of a textual
+        strategy then change every epoch: the name-keyed cache is neither read nor filled, the look-ahead encode runs instead."""
         classes, ids, lut = self._class_space(only_seen)
         if self.modality in ("text", "multi"):
             # features() / predict() / trained_features() re-point model.classes at their own class list between epochs; the eager fallback of a
             # graphed step (ragged last batch) reads it at call time, so it is re-set here every epoch, not only when the graph is (re)built
             self.model.classes = classes
         accum = int(getattr(self.config, "ACCUMULATION_ITER", 1))
+        aug = self.view_sampler()
         if accum != 1 or not getattr(self.config, "GRAPH_STEPS", True):
-            return self._train_epoch_eager(train_loader, classes, ids, lut, accum)
+            return self._train_epoch_eager(train_loader, classes, ids, lut, accum, aug, epoch)
         g = self._graphed_step(classes)
         total = torch.zeros((), dtype=torch.float64, device=self.device)      # the sum the eager loop forms in Python doubles
         correct = torch.zeros((), dtype=torch.int64, device=self.device)
@@ -341,10 +361,13 @@ class TrainingStrategy:
         def batches():
             for img, _, _, label, names in train_loader:
                 w = self.row_weights(label.tolist(), names)          # labels are still on the host here: no synchronisation
-                yield img.to(self.device, non_blocking=True), label.to(self.device, non_blocking=True), w.to(self.device, non_blocking=True), list(names)
+                img = img.to(self.device, non_blocking=True)
+                if aug is not None:
+                    img = aug.batch(img.contiguous(), names, epoch)
+                yield img, label.to(self.device, non_blocking=True), w.to(self.device, non_blocking=True), list(names)
 
         if self.modality == "text":
-            if getattr(self.config, "CACHE_FROZEN_FEATURES", True):
+            if aug is None and getattr(self.config, "CACHE_FROZEN_FEATURES", True):
                 stream = ((self.frozen_image_features(img, names), label, w) for img, label, w, names in batches())
             else:           # every image is encoded every time it is used, a group of batches per frozen-tower forward
                 stream = steps.lookahead_image_features(self.clip_model, ((img, label, w) for img, label, w, _ in batches()),
@@ -366,11 +389,13 @@ class TrainingStrategy:
         total, correct, count, n_batches = t.tolist()
         return total / max(n_batches, 1.0), correct / max(count, 1.0)
 
-    def _train_epoch_eager(self, train_loader, classes, ids, lut, accum):
+    def _train_epoch_eager(self, train_loader, classes, ids, lut, accum, aug=None, epoch=0):
         total, correct, count = 0.0, 0, 0
         for i, (img, _, _, label, names) in enumerate(train_loader):
             img, label = img.to(self.device), label.to(self.device)
-            image_features, text_features = self.features(img, classes, list(names))
+            if aug is not None:
+                img = aug.batch(img.contiguous(), names, epoch)
+            image_features, text_features = self.features(img, classes, None if aug is not None else list(names))      # views are never cached by name
             logits = steps.CosineHeadFn.apply(image_features, text_features, self.scale())
             w = self.row_weights(label.tolist(), names).to(self.device)
             loss = steps.WeightedCEFn.apply(logits, lut[label], w) / accum
@@ -415,7 +440,7 @@ class TrainingStrategy:
         loader = self._loader(train_data, True)
         best_acc, best_prompt = -1.0, None
         for epoch in range(int(self.config.EPOCHS)):
-            loss, acc = self._train_epoch(loader, only_seen=only_seen)
+            loss, acc = self._train_epoch(loader, only_seen=only_seen, epoch=epoch)
             val_acc = self._run_validation(val_data, only_seen=only_seen) if val_data is not None and len(val_data) else acc
             log.info(f"epoch {epoch}: loss {loss:.4f} train acc {acc:.3f} val acc {val_acc:.3f}")
             if val_acc > best_acc:

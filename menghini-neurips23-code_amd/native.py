@@ -91,6 +91,8 @@ _SIGS = {
     "grip_preprocess_image": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                       c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "grip_preprocess_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    # (ABI 9 addition) train-time views: crop box -> Pillow bicubic resample -> optional mirror, [n_views] descriptors on the device (csrc/augment.hip)
+    "grip_augment_views": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "grip_leaderboard_scan": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, POINTER(c_int64)]),
     "grip_leaderboard_scan_bounded": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_int, c_int, c_int64, c_int, c_int64, c_void_p, c_void_p,
                                               POINTER(c_int64), c_void_p, POINTER(c_int64)]),

@@ -46,3 +46,13 @@ def integers(seed: int, stream: int, shape, lo, hi) -> np.ndarray:
     n = int(np.prod(shape)) if len(shape) else 1
     u = uniform(seed, stream, n)
     return np.minimum((lo + np.floor((hi - lo) * (1.0 - u))).astype(np.int64), hi - 1).reshape(shape)
+
+
+def uniform_at(seed: int, stream: int, counter, n: int) -> np.ndarray:
+    """n float64 uniforms in (0, 1] from the Philox block that starts at `counter` = (c1, c2, c3): the upper three 64-bit words of the 256-bit
+    counter, the lowest word counts the blocks drawn.  `uniform(seed, stream, n)` is `uniform_at(seed, stream, (0, 0, 0), n)`; draws at different
+    counters of one (seed, stream) are independent streams that need no draws before them (grip_amd.augment keys them by epoch and view)."""
+    c1, c2, c3 = (int(c) for c in counter)
+    bg = np.random.Philox(key=np.array([seed, stream], dtype=np.uint64), counter=np.array([0, c1, c2, c3], dtype=np.uint64))
+    raw = bg.random_raw(n)
+    return ((raw >> np.uint64(11)).astype(np.float64) + 1.0) * (1.0 / 9007199254740992.0)
