@@ -80,6 +80,25 @@ int grip_debug_attention_row_exact(const void* qkv, const void* qrows, const int
                                    void* stream);
 /* out[M,d] (f16) = LayerNorm(x[M,d] f32; gamma, beta), eps 1e-5. */
 int grip_debug_layernorm(const float* x, const float* gamma, const float* beta, void* out, int M, int d, void* stream);
+/* The backward row kernels (csrc/rowops_bwd.hip) through the launchers the towers call (tests/test_gpu_rowops_bwd.py).  x is f16, dxh f16, everything
+ * else f32; widths d % 4 == 0, d <= 2048.  ln_bwd_add: dx[r] += LNbwd(sum_p dln[p * part_stride + r d ..]; x[r]), dxh = f16(dx), r < M.  ln_bwd_init:
+ * dx[r] = LNbwd(..) + (r == b stride + index[b] ? rows_add[b] : 0), b = r / stride (index NULL: position 0). */
+int grip_debug_ln_bwd_add(const void* x, const float* dln, int parts, int64_t part_stride, const float* gamma, float* dx, void* dxh, int M, int d, void* stream);
+int grip_debug_ln_bwd_init(const void* x, const float* dln, int parts, int64_t part_stride, const float* gamma, const float* rows_add, const int32_t* index,
+                           int stride, float* dx, void* dxh, int M, int d, void* stream);
+/* dx[b stride + index[b]] = LNbwd(dy[b]; x[that row]), b < n.  fill = 0: only those n rows are written (first, M unused); fill = 1: every row r < M is
+ * written, zero where it is no read row (sequences start at row `first`, first <= index[b] < first + stride). */
+int grip_debug_ln_bwd_scatter(const void* x, const float* dy, const int32_t* index, int stride, int first, const float* gamma, float* dx, void* dxh, int n, int M,
+                              int d, int fill, void* stream);
+/* Visual prompt slice of dx [B*S, d] (rows b S + 1 + s).  mode 0: grad [P, d] = scale[1] sum_b LNbwd(dx row; prefix[s]); 1: per image, prefix and grad
+ * [B, P, d]; 2: a deep prompt's slice, grad [P, d] = scale[1] sum_b dx row, the rows read then zeroed in dx and dxh (modes 0, 1 touch neither). */
+int grip_debug_vit_prefix_grad(float* dx, void* dxh, const float* prefix, const float* gamma, const float* scale, float* grad, int B, int S, int P, int d, int mode,
+                               void* stream);
+/* Textual prompt slice of dx [C*T, d] (rows c T + 1 + p): grad [prefix_classes, P, d] = scale[1] x (the sum over classes in class order when
+ * prefix_classes == 1, the class's own row when == C).  deep != 0: the rows summed are then zeroed in dx and dxh. */
+int grip_debug_text_prefix_grad(float* dx, void* dxh, const float* scale, float* grad, int C, int T, int P, int prefix_classes, int d, int deep, void* stream);
+/* scale[0] = 2^k with amax|g| 2^k in [32, 64) (|k| <= 40; k = 0 for a zero or non-finite amax), scale[1] = 2^-k, g16 = f16(g scale[0]). */
+int grip_debug_grad_scale_cast(const float* g, void* g16, float* scale, int n, void* stream);
 
 /* GEMM launch profiler: while enabled, every 4th GEMM launch is bracketed by HIP events on its stream. */
 int grip_profile_enable(int on);

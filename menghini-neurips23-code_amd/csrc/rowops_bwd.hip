@@ -85,8 +85,11 @@ __device__ __forceinline__ void ln_bwd_row(const XT* __restrict__ xr, const f32x
 }
 
 // The same row with the loads where they are used (the form until r04): fewer registers in flight, more waves per CU -- what the bandwidth-bound
-// launches want (image tower, M = 3 408 rows x 768, three partials: 63 MB per launch; 11.5 us this way, 13.0 with everything in flight).  Same
-// arithmetic in the same order: the two forms return the same bits.
+// launches want (image tower, M = 3 408 rows x 768, three partials: 63 MB per launch; 11.5 us this way, 13.0 with everything in flight).  The same
+// operations in the same source order, but NOT always the same bits: HIP compiles with fp-contract=fast and the compiler fuses other multiply-add pairs
+// in the two forms of some instantiations (NV = 3: 20 + 12 v_fma / v_fmac in ln_bwd_row against 16 + 13 here), so at d = 768 one element in twenty
+// differs in bits between an M <= 1024 and an M > 1024 launch, while at d = 512 (NV = 2) none does.  Each form is deterministic and within the derived
+// bound of the float64 value (tests/test_gpu_rowops_bwd.py, DESIGN "Row backward kernel tests").
 template <int NV, typename XT>
 __device__ __forceinline__ void ln_bwd_row_stream(const XT* __restrict__ xr, const f32x4* __restrict__ dyr, const f32x4* __restrict__ gamma,
                                                   int lane, int d4, int d, f32x4 (&dx)[NV], int parts, size_t part_stride4) {
@@ -458,6 +461,7 @@ int launch_ln_bwd_scatter_fill(const resid_t* x, const float* dy, const int32_t*
     return GRIP_OK;
 }
 int launch_vit_prefix_grad(const float* dx, const float* prefix, const float* gamma, const float* scale, float* grad, int B, int S, int P, int d, hipStream_t s) {
+    GRIP_REQUIRE(B > 0 && P > 0 && S >= 1 + P, "vit_prefix_grad: bad shape (B=%d P=%d S=%d)", B, P, S);
     DISPATCH_NV_B(d, hipLaunchKernelGGL(vit_prefix_grad_kernel<NV>, dim3(P), dim3(512), 0, s, dx, prefix, gamma, scale, grad, B, S, P, d));
     GRIP_CHECK_HIP(hipGetLastError());
     return GRIP_OK;
@@ -477,6 +481,8 @@ int launch_vit_prefix_grad_per_image(const float* dx, const float* prefix, const
     return GRIP_OK;
 }
 int launch_text_prefix_grad(const float* dx, const float* scale, float* grad, int C, int T, int P, int prefix_classes, int d, hipStream_t s) {
+    GRIP_REQUIRE(C > 0 && P > 0 && T > 1 + P && d % 4 == 0 && (prefix_classes == 1 || prefix_classes == C),
+                 "text_prefix_grad: bad arguments (C=%d T=%d P=%d prefix_classes=%d d=%d)", C, T, P, prefix_classes, d);
     const int waves = prefix_classes * P * ((d / 4 + 63) / 64);
     hipLaunchKernelGGL(text_prefix_grad_kernel<>, dim3((waves + 3) / 4), dim3(256), 0, s, dx, scale, grad, C, T, P, prefix_classes, d, (half_t*)nullptr);
     GRIP_CHECK_HIP(hipGetLastError());

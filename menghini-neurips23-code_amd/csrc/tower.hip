@@ -867,6 +867,37 @@ extern "C" int grip_debug_attention_row_exact(const void* qkv, const void* qrows
 extern "C" int grip_debug_layernorm(const float* x, const float* gamma, const float* beta, void* out, int M, int d, void* stream) {
     return launch_layernorm_f16_from_f32(x, gamma, beta, (half_t*)out, M, d, (hipStream_t)stream);
 }
+// The backward row kernels (csrc/rowops_bwd.hip) through their launchers (tests/test_gpu_rowops_bwd.py).  x f16, everything else f32; dxh f16.
+extern "C" int grip_debug_ln_bwd_add(const void* x, const float* dln, int parts, int64_t part_stride, const float* gamma, float* dx, void* dxh, int M, int d,
+                                     void* stream) {
+    return launch_ln_bwd_add((const resid_t*)x, dln, parts, part_stride, gamma, dx, (half_t*)dxh, M, d, (hipStream_t)stream);
+}
+extern "C" int grip_debug_ln_bwd_init(const void* x, const float* dln, int parts, int64_t part_stride, const float* gamma, const float* rows_add,
+                                      const int32_t* index, int stride, float* dx, void* dxh, int M, int d, void* stream) {
+    return launch_ln_bwd_init((const resid_t*)x, dln, parts, part_stride, gamma, rows_add, index, stride, dx, (half_t*)dxh, M, d, (hipStream_t)stream);
+}
+// fill = 0: ln_bwd_scatter (writes the n read rows only; first and M unused), fill = 1: ln_bwd_scatter_fill (writes every row r < M)
+extern "C" int grip_debug_ln_bwd_scatter(const void* x, const float* dy, const int32_t* index, int stride, int first, const float* gamma, float* dx, void* dxh,
+                                         int n, int M, int d, int fill, void* stream) {
+    if (fill) return launch_ln_bwd_scatter_fill((const resid_t*)x, dy, index, stride, first, gamma, dx, (half_t*)dxh, n, M, d, (hipStream_t)stream);
+    return launch_ln_bwd_scatter((const resid_t*)x, dy, index, stride, gamma, dx, (half_t*)dxh, n, d, (hipStream_t)stream);
+}
+// mode 0: shared prompts (prefix [P, d]), 1: per-image prompts (prefix and grad [B, P, d]), 2: a deep prompt's slice (no LayerNorm; zeroes the rows read in dx and dxh)
+extern "C" int grip_debug_vit_prefix_grad(float* dx, void* dxh, const float* prefix, const float* gamma, const float* scale, float* grad, int B, int S, int P,
+                                          int d, int mode, void* stream) {
+    if (mode == 0) return launch_vit_prefix_grad(dx, prefix, gamma, scale, grad, B, S, P, d, (hipStream_t)stream);
+    if (mode == 1) return launch_vit_prefix_grad_per_image(dx, prefix, gamma, scale, grad, B, S, P, d, (hipStream_t)stream);
+    return launch_vit_deep_grad(dx, (half_t*)dxh, scale, grad, B, S, P, d, (hipStream_t)stream);
+}
+// deep = 0: text_prefix_grad (dxh unused), 1: text_deep_grad (zeroes the rows summed in dx and dxh)
+extern "C" int grip_debug_text_prefix_grad(float* dx, void* dxh, const float* scale, float* grad, int C, int T, int P, int prefix_classes, int d, int deep,
+                                           void* stream) {
+    if (deep) return launch_text_deep_grad(dx, (half_t*)dxh, scale, grad, C, T, P, prefix_classes, d, (hipStream_t)stream);
+    return launch_text_prefix_grad(dx, scale, grad, C, T, P, prefix_classes, d, (hipStream_t)stream);
+}
+extern "C" int grip_debug_grad_scale_cast(const float* g, void* g16, float* scale, int n, void* stream) {
+    return launch_grad_scale_cast(g, (half_t*)g16, scale, n, (hipStream_t)stream);
+}
 
 // ---------------------------------------------------------------------------------------------- backward
 // Input-gradient chain of one tower down to its prompt slice.  Enters with dx / dxh holding the
