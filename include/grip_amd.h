@@ -220,14 +220,18 @@ int grip_cosine_head(const float* img_emb, const float* txt_emb, float scale, in
                      float* txt_norm_scratch, void* stream);
 
 /* Backward of logits = scale * normalize(img) @ normalize(txt).T :
- * grad_logits [n, c] -> grad_img [n, e] and/or grad_txt [c, e] (either may be NULL). */
+ * grad_logits [n, c] -> grad_img [n, e] and/or grad_txt [c, e] (either may be NULL).  grad_logits is used as given: it carries no
+ * labels, so a row whose label grip_weighted_ce found outside [0, c) arrives here as w_i * softmax (no one-hot subtracted) and
+ * contributes that to both gradients. */
 int grip_cosine_head_backward(const float* img_emb, const float* txt_emb, float scale, int n, int c, int e,
                               const float* grad_logits, float* grad_img, float* grad_txt, void* stream);
 
 /* Mean cross-entropy over the rows with row_weight != 0, each weighted: the three FPL losses
  * (methods/semi_supervised_learning/textual_fpl.py:123-165, methods/transductive_zsl/textual_fpl.py:117-147,
  * methods/unsupervised_learning/visual_fpl.py:107-122) are sums of two such masked means; the host
- * passes per-row weights w_i = gamma_group / |group|.  loss [1] f32, grad_logits [n, c] f32. */
+ * passes per-row weights w_i = gamma_group / |group|.  loss [1] f32, grad_logits [n, c] f32 or NULL.
+ * A label outside [0, c) is not an error: the row is left out of the loss (as a row of weight 0 is) and no one-hot is
+ * subtracted from its gradient row, which is w_i * softmax(logits_i).  All weights zero: the loss is exactly 0. */
 int grip_weighted_ce(const float* logits, const int32_t* labels, const float* row_weight, int n, int c,
                      float* loss, float* grad_logits, void* stream);
 

@@ -16,7 +16,7 @@ extern "C" {
 int grip_debug_gemm(int epi, const void* A, const void* W, int M, int N, int K, const float* bias, const void* resid,
                     const void* aux, void* out, void* out2, float scalar, int m_pad, int variant, void* stream);
 /* The LayerNorm-carrying epilogues (csrc/gemm.hip).  epi 3 with stat_part != NULL: the residual epilogue also writes, per row
- * and 64-column tile, (sum, sum of squares) of the stored values to stat_part [M, N/64, 2].  epi 7 / 8: LayerNorm folded into
+ * and 64-column tile, (sum, sum of squares) of the stored values to stat_part [N/64, M, 2].  epi 7 / 8: LayerNorm folded into
  * the GEMM: out = [quickgelu](rstd_r (A W'^T - mean_r colsum) + bias) with rowstat [M, 2] = (mean, rstd), A = the raw rows. */
 int grip_debug_gemm_ln(int epi, const void* A, const void* W, int M, int N, int K, const float* bias, const void* resid, void* out, void* out2,
                        float* stat_part, const float* rowstat, const float* colsum, int m_pad, int variant, void* stream);
@@ -41,7 +41,7 @@ int grip_debug_gemm_splitk(const void* A, const void* W, int M, int N, int K, fl
 int grip_debug_gemm_plan(int epi, int M, int N, int K, int ldc, int64_t m_pad, int variant, int ksplit, int f32, int rot_rows, int present,
                          int stat_parts, int64_t split_stride, int n_cu, char* text, int text_len);
 /* Wg = f16(gamma o W) [N, K], colsum[n] = sum_k Wg[n][k], bias_out = bias + W beta; then, if stat_part != NULL,
- * rowstat [M, 2] = (mean, rstd) from the [M, parts, 2] partial sums over rows of width d. */
+ * rowstat [M, 2] = (mean, rstd) from the [parts, M, 2] partial sums over rows of width d.  W == NULL: the statistics alone. */
 int grip_debug_ln_fold(const void* W, const float* gamma, const float* beta, const float* bias, void* Wg, float* colsum, float* bias_out,
                        int N, int K, const float* stat_part, int parts, float* rowstat, int M, int d, void* stream);
 /* The split-f16 GEMM of precision-2 towers (csrc/gemm_split.hip) on f32 inputs: A [m_pad, K] and W [N, K] are rewritten in the split layout
@@ -99,6 +99,31 @@ int grip_debug_vit_prefix_grad(float* dx, void* dxh, const float* prefix, const 
 int grip_debug_text_prefix_grad(float* dx, void* dxh, const float* scale, float* grad, int C, int T, int P, int prefix_classes, int d, int deep, void* stream);
 /* scale[0] = 2^k with amax|g| 2^k in [32, 64) (|k| <= 40; k = 0 for a zero or non-finite amax), scale[1] = 2^-k, g16 = f16(g scale[0]). */
 int grip_debug_grad_scale_cast(const float* g, void* g16, float* scale, int n, void* stream);
+/* The forward row kernels (csrc/rowops.hip) through the launchers the towers call (tests/test_gpu_rowops_fwd.py); widths d % 4 == 0, d <= 2048.
+ * LayerNorm of M rows, eps 1e-5.  f32 = 0: x f16 (the residual stream) -> out f16; 1: x f32 -> out f32; 2: x f32 -> out in the split layout (4 bytes per
+ * element, d % 32 == 0).  gather = 0: row r reads x[r] (launch_layernorm_f16; row_index and row_stride unused).  gather = 1: row r reads
+ * x[r * row_stride + (row_index ? row_index[r] : 0)] (launch_gather_ln_f16, the CLS / EOT form; f32 = 2 writes f32 as f32 = 1 does). */
+int grip_debug_layernorm_modes(const void* x, const int32_t* row_index, int row_stride, const float* gamma, const float* beta, void* out, int f32, int gather,
+                               int M, int d, void* stream);
+/* Vision sequence assembly + ln_pre: x [B (1 + P + G2), d] (f32 != 0: f32, else f16) from patch_out [B G2, d], cls [d], pos [1 + G2, d] or NULL,
+ * prefix [P, d] or, per_image != 0, [B, P, d]; rowstat [rows, 2] or NULL; x_lo [rows, d] f16 or NULL (f16 stream only). */
+int grip_debug_vit_assemble(const float* patch_out, const float* cls, const float* pos, const float* prefix, int P, const float* gamma, const float* beta, void* x,
+                            int f32, float* rowstat, int B, int G2, int d, void* x_lo, int per_image, void* stream);
+/* Deep prompt rows written into a stream x of M rows.  text = 0 (launch_vit_deep_insert): rows b S + 1 + p := deep[p], b < B; prefix_classes and
+ * shared_rows unused.  text != 0 (launch_text_deep_insert): B classes, deep [prefix_classes, P, d], shared_rows = 0 or P + 1 (x_lo unused).  stat_part
+ * [d / 64, M, 2] and rowstat [M, 2] (each optional, f16 stream, d % 64 == 0): the statistics of the rows written. */
+int grip_debug_deep_insert(const float* deep, int prefix_classes, void* x, int f32, void* x_lo, float* stat_part, float* rowstat, int B, int S, int P, int shared_rows,
+                           int M, int d, int text, void* stream);
+/* Token embedding + prompt splice: x [shared_rows + C (T - shared_rows), d] from ids [C, ld_ids] (clamped to [0, vocab)), tok_emb [vocab, d], pos [T, d] or NULL,
+ * prefix [prefix_classes, P, d]; rowstat [rows, 2] or NULL. */
+int grip_debug_text_embed(const int32_t* ids, int ld_ids, const float* tok_emb, const float* pos, const float* prefix, int P, int prefix_classes, void* x, int f32,
+                          float* rowstat, int C, int T, int d, int vocab, int shared_rows, void* stream);
+/* Patch gather: out [B (R / patch)^2, Kpad] (out_f32 ? f32 : f16) from images [B, 3, R, R] (images_f16 ? f16 : f32), columns >= 3 patch^2 zero. */
+int grip_debug_patch_gather(const void* images, int images_f16, void* out, int out_f32, int B, int R, int patch, int Kpad, void* stream);
+/* out [cols, rows] = in [rows, cols]^T, in rows ld_in elements apart (f32 ? f32 : f16). */
+int grip_debug_transpose(const void* in, void* out, int f32, int rows, int cols, int ld_in, void* stream);
+/* out[b] = x[b * row_stride + (row_index ? row_index[b] : 0)], rows of width d: f16 elements (d % 8 == 0), or four_byte != 0: 4-byte elements (d % 4 == 0). */
+int grip_debug_gather_rows(const void* x, const int32_t* row_index, int row_stride, void* out, int n_rows, int d, int four_byte, void* stream);
 
 /* GEMM launch profiler: while enabled, every 4th GEMM launch is bracketed by HIP events on its stream. */
 int grip_profile_enable(int on);

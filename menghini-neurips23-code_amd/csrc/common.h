@@ -211,7 +211,7 @@ int launch_vit_deep_insert(const float* deep, void* x, int f32, half_t* x_lo, fl
 // layout (shared_rows = P + 1, prefix_classes = 1) writes its P rows once.  (seq_row is declared below; M = rows of the stream)
 int launch_text_deep_insert(const float* deep, int prefix_classes, void* x, int f32, float* stat_part, float* rowstat, int C, int S, int P, int shared_rows, int M, int d,
                             hipStream_t s);
-// rowstat [M, 2] = (mean, rstd) of every row from the [M, parts, 2] partial sums the residual GEMM epilogues emit
+// rowstat [M, 2] = (mean, rstd) of every row from the [parts, M, 2] partial sums the residual GEMM epilogues emit
 int launch_ln_stats_finalize(const float* stat_part, int parts, float* rowstat, int M, int d, hipStream_t s);
 // W' = f16(gamma o W) [N, K]; colsum[n] = sum_k W'[n][k]; bias_out[n] = bias[n] + sum_k beta[k] W[n][k]
 int launch_ln_fold_weights(const half_t* W, const float* gamma, const float* beta, const float* bias, half_t* Wg, float* colsum, float* bias_out,

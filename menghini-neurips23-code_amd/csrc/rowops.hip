@@ -52,6 +52,7 @@ __global__ __launch_bounds__(256) void ln_f16_kernel(const XT* __restrict__ x, c
     } while (0)
 
 int launch_layernorm_f16(const void* x, const float* gamma, const float* beta, void* out, int f32, int M, int d, hipStream_t s) {
+    GRIP_REQUIRE(x && gamma && beta && out && M > 0 && d > 0, "layernorm: null pointer or empty input (M=%d d=%d)", M, d);
     if (f32 == 2) {
         GRIP_REQUIRE(d % 32 == 0, "layernorm (split layout): width %d %% 32 != 0", d);
         DISPATCH_NV(d, hipLaunchKernelGGL((ln_f16_kernel<NV, float, half_t, true>), dim3((M + 3) / 4), dim3(256), 0, s, (const float*)x, (const int32_t*)nullptr, 1, gamma, beta, (half_t*)out, M, d));
@@ -65,6 +66,7 @@ int launch_layernorm_f16(const void* x, const float* gamma, const float* beta, v
 }
 
 int launch_layernorm_f16_from_f32(const float* x, const float* gamma, const float* beta, half_t* out, int M, int d, hipStream_t s) {
+    GRIP_REQUIRE(x && gamma && beta && out && M > 0 && d > 0, "layernorm: null pointer or empty input (M=%d d=%d)", M, d);
     DISPATCH_NV(d, hipLaunchKernelGGL((ln_f16_kernel<NV, float>), dim3((M + 3) / 4), dim3(256), 0, s, x, (const int32_t*)nullptr, 1, gamma, beta, out, M, d));
     GRIP_CHECK_HIP(hipGetLastError());
     return GRIP_OK;
@@ -72,6 +74,7 @@ int launch_layernorm_f16_from_f32(const float* x, const float* gamma, const floa
 
 int launch_gather_ln_f16(const void* x, const int32_t* row_index, int row_stride, const float* gamma, const float* beta,
                          void* out, int f32, int n_rows, int d, hipStream_t s) {
+    GRIP_REQUIRE(x && gamma && beta && out && n_rows > 0 && d > 0 && row_stride > 0, "gather_ln: null pointer or bad shape (rows=%d d=%d row stride=%d)", n_rows, d, row_stride);
     if (f32) {
         DISPATCH_NV(d, hipLaunchKernelGGL((ln_f16_kernel<NV, float, float>), dim3((n_rows + 3) / 4), dim3(256), 0, s, (const float*)x, row_index, row_stride, gamma, beta, (float*)out, n_rows, d));
     } else {
@@ -137,6 +140,8 @@ __global__ __launch_bounds__(256) void vit_assemble_ln_kernel(const float* __res
 int launch_vit_assemble_ln(const float* patch_out, const float* cls, const float* pos, const float* prefix, int P,
                            const float* gamma, const float* beta, void* x, int f32, float* rowstat, int B, int G2, int d, hipStream_t s, half_t* x_lo,
                            int per_image) {
+    GRIP_REQUIRE(patch_out && cls && gamma && beta && x && (P == 0 || prefix), "vit_assemble_ln: null pointer");
+    GRIP_REQUIRE(B > 0 && P >= 0 && G2 > 0 && d > 0, "vit_assemble_ln: bad shape (B=%d P=%d G2=%d d=%d)", B, P, G2, d);
     const int rows = B * (1 + P + G2);
     const int64_t prefix_stride = per_image ? (int64_t)P * d : 0;
     if (f32) {
@@ -285,7 +290,9 @@ __global__ __launch_bounds__(256) void text_embed_kernel(const int32_t* __restri
 
 int launch_text_embed(const int32_t* token_ids, int ld_ids, const float* tok_emb, const float* pos, const float* prefix, int P,
                       int prefix_classes, void* x, int f32, float* rowstat, int C, int T, int d, int vocab, hipStream_t s, int shared_rows) {
-    GRIP_REQUIRE(d % 4 == 0, "text_embed: width %% 4 != 0");
+    GRIP_REQUIRE(d > 0 && d % 4 == 0, "text_embed: width %% 4 != 0");
+    GRIP_REQUIRE(token_ids && tok_emb && x && (P == 0 || prefix), "text_embed: null pointer");
+    GRIP_REQUIRE(C > 0 && P >= 0 && T > P && ld_ids >= T && vocab > 0, "text_embed: bad shape (C=%d T=%d P=%d ld_ids=%d vocab=%d)", C, T, P, ld_ids, vocab);
     GRIP_REQUIRE(shared_rows == 0 || (shared_rows == P + 1 && prefix_classes == 1 && shared_rows < T), "text_embed: shared-prefix layout needs one shared context and shared rows = n_prefix + 1 < T");
     const int rows = shared_rows + C * (T - shared_rows);
     if (f32)
@@ -348,7 +355,8 @@ __global__ __launch_bounds__(256) void im2col_kernel(const T* __restrict__ img, 
 }
 
 int launch_im2col(const void* images, int images_f16, void* out, int out_f32, int B, int R, int patch, int Kpad, hipStream_t s) {
-    GRIP_REQUIRE(R % patch == 0 && Kpad % 8 == 0, "im2col: bad geometry R=%d patch=%d", R, patch);
+    GRIP_REQUIRE(images && out && B > 0, "im2col: null pointer or empty batch");
+    GRIP_REQUIRE(patch > 0 && patch <= R && R % patch == 0 && Kpad % 8 == 0 && Kpad >= 3 * patch * patch, "im2col: bad geometry R=%d patch=%d Kpad=%d", R, patch, Kpad);
     const int G = R / patch;
     const size_t total = (size_t)B * G * G * (Kpad / 8);
     int blocks = (int)((total + 255) / 256);
@@ -385,6 +393,7 @@ __global__ __launch_bounds__(256) void transpose_kernel(const T* __restrict__ in
 }
 
 int launch_transpose(const void* in, void* out, int f32, int rows, int cols, int ld_in, hipStream_t s) {
+    GRIP_REQUIRE(in && out && rows > 0 && cols > 0 && ld_in >= cols, "transpose: null pointer or bad shape (rows=%d cols=%d ld_in=%d)", rows, cols, ld_in);
     if (f32)
         hipLaunchKernelGGL(transpose_kernel<float>, dim3((cols + 63) / 64, (rows + 63) / 64), dim3(256), 0, s, (const float*)in, (float*)out, rows, cols, ld_in);
     else
@@ -416,6 +425,7 @@ __global__ __launch_bounds__(256) void ln_stats_finalize_kernel(const float* __r
 }
 
 int launch_ln_stats_finalize(const float* stat_part, int parts, float* rowstat, int M, int d, hipStream_t s) {
+    GRIP_REQUIRE(stat_part && rowstat && parts > 0 && M > 0 && d > 0, "ln_stats_finalize: null pointer or bad shape (parts=%d M=%d d=%d)", parts, M, d);
     hipLaunchKernelGGL(ln_stats_finalize_kernel, dim3((M + 255) / 256), dim3(256), 0, s, stat_part, parts, rowstat, M, 1.0f / (float)d);
     GRIP_CHECK_HIP(hipGetLastError());
     return GRIP_OK;
@@ -445,6 +455,7 @@ __global__ __launch_bounds__(256) void ln_fold_weights_kernel(const half_t* __re
 
 int launch_ln_fold_weights(const half_t* W, const float* gamma, const float* beta, const float* bias, half_t* Wg, float* colsum, float* bias_out,
                            int N, int K, hipStream_t s) {
+    GRIP_REQUIRE(W && gamma && beta && bias && Wg && colsum && bias_out && N > 0 && K > 0, "ln_fold_weights: null pointer or bad shape (N=%d K=%d)", N, K);
     hipLaunchKernelGGL(ln_fold_weights_kernel, dim3((N + 3) / 4), dim3(256), 0, s, W, gamma, beta, bias, Wg, colsum, bias_out, N, K);
     GRIP_CHECK_HIP(hipGetLastError());
     return GRIP_OK;
@@ -470,14 +481,14 @@ __global__ __launch_bounds__(256) void gather_rows4_kernel(const f32x4* __restri
     out[(size_t)b * d4 + c] = x[src * d4 + c];
 }
 int launch_gather_rows4(const void* x, const int32_t* row_index, int row_stride, void* out, int n_rows, int d, hipStream_t s) {
-    GRIP_REQUIRE(d % 4 == 0, "gather_rows4: width %% 4 != 0");
+    GRIP_REQUIRE(x && out && n_rows > 0 && row_stride > 0 && d > 0 && d % 4 == 0, "gather_rows4: null pointer or bad shape (rows=%d row stride=%d d=%d; width %% 4 != 0?)", n_rows, row_stride, d);
     hipLaunchKernelGGL(gather_rows4_kernel, dim3((n_rows * (d / 4) + 255) / 256), dim3(256), 0, s, (const f32x4*)x, row_index, row_stride, (f32x4*)out, n_rows, d / 4);
     GRIP_CHECK_HIP(hipGetLastError());
     return GRIP_OK;
 }
 
 int launch_gather_rows(const half_t* x, const int32_t* row_index, int row_stride, half_t* out, int n_rows, int d, hipStream_t s) {
-    GRIP_REQUIRE(d % 8 == 0, "gather_rows: width %% 8 != 0");
+    GRIP_REQUIRE(x && out && n_rows > 0 && row_stride > 0 && d > 0 && d % 8 == 0, "gather_rows: null pointer or bad shape (rows=%d row stride=%d d=%d; width %% 8 != 0?)", n_rows, row_stride, d);
     hipLaunchKernelGGL(gather_rows_kernel, dim3((n_rows * (d / 8) + 255) / 256), dim3(256), 0, s, x, row_index, row_stride, out, n_rows, d / 8);
     GRIP_CHECK_HIP(hipGetLastError());
     return GRIP_OK;

@@ -812,7 +812,7 @@ extern "C" int grip_debug_gemm_train(int epi, const void* A, const void* W, int 
 extern "C" int grip_debug_coop_split(int M, int N, int K) { return gemm_pick_coop_split(M, N, K); }
 extern "C" int grip_debug_ln_fold(const void* W, const float* gamma, const float* beta, const float* bias, void* Wg, float* colsum, float* bias_out,
                                   int N, int K, const float* stat_part, int parts, float* rowstat, int M, int d, void* stream) {
-    int rc = launch_ln_fold_weights((const half_t*)W, gamma, beta, bias, (half_t*)Wg, colsum, bias_out, N, K, (hipStream_t)stream);
+    int rc = W ? launch_ln_fold_weights((const half_t*)W, gamma, beta, bias, (half_t*)Wg, colsum, bias_out, N, K, (hipStream_t)stream) : GRIP_OK;     // W == NULL: the statistics alone
     if (rc || !stat_part) return rc;
     return launch_ln_stats_finalize(stat_part, parts, rowstat, M, d, (hipStream_t)stream);
 }
@@ -897,6 +897,36 @@ extern "C" int grip_debug_text_prefix_grad(float* dx, void* dxh, const float* sc
 }
 extern "C" int grip_debug_grad_scale_cast(const float* g, void* g16, float* scale, int n, void* stream) {
     return launch_grad_scale_cast(g, (half_t*)g16, scale, n, (hipStream_t)stream);
+}
+// The forward row kernels (csrc/rowops.hip) through their launchers (tests/test_gpu_rowops_fwd.py).
+extern "C" int grip_debug_layernorm_modes(const void* x, const int32_t* row_index, int row_stride, const float* gamma, const float* beta, void* out, int f32,
+                                          int gather, int M, int d, void* stream) {
+    if (gather) return launch_gather_ln_f16(x, row_index, row_stride, gamma, beta, out, f32, M, d, (hipStream_t)stream);
+    return launch_layernorm_f16(x, gamma, beta, out, f32, M, d, (hipStream_t)stream);
+}
+extern "C" int grip_debug_vit_assemble(const float* patch_out, const float* cls, const float* pos, const float* prefix, int P, const float* gamma, const float* beta,
+                                       void* x, int f32, float* rowstat, int B, int G2, int d, void* x_lo, int per_image, void* stream) {
+    return launch_vit_assemble_ln(patch_out, cls, pos, prefix, P, gamma, beta, x, f32, rowstat, B, G2, d, (hipStream_t)stream, (half_t*)x_lo, per_image);
+}
+// text = 0: launch_vit_deep_insert; else launch_text_deep_insert with B classes
+extern "C" int grip_debug_deep_insert(const float* deep, int prefix_classes, void* x, int f32, void* x_lo, float* stat_part, float* rowstat, int B, int S, int P,
+                                      int shared_rows, int M, int d, int text, void* stream) {
+    if (text) return launch_text_deep_insert(deep, prefix_classes, x, f32, stat_part, rowstat, B, S, P, shared_rows, M, d, (hipStream_t)stream);
+    return launch_vit_deep_insert(deep, x, f32, (half_t*)x_lo, stat_part, rowstat, B, S, P, M, d, (hipStream_t)stream);
+}
+extern "C" int grip_debug_text_embed(const int32_t* ids, int ld_ids, const float* tok_emb, const float* pos, const float* prefix, int P, int prefix_classes, void* x,
+                                     int f32, float* rowstat, int C, int T, int d, int vocab, int shared_rows, void* stream) {
+    return launch_text_embed(ids, ld_ids, tok_emb, pos, prefix, P, prefix_classes, x, f32, rowstat, C, T, d, vocab, (hipStream_t)stream, shared_rows);
+}
+extern "C" int grip_debug_patch_gather(const void* images, int images_f16, void* out, int out_f32, int B, int R, int patch, int Kpad, void* stream) {
+    return launch_im2col(images, images_f16, out, out_f32, B, R, patch, Kpad, (hipStream_t)stream);
+}
+extern "C" int grip_debug_transpose(const void* in, void* out, int f32, int rows, int cols, int ld_in, void* stream) {
+    return launch_transpose(in, out, f32, rows, cols, ld_in, (hipStream_t)stream);
+}
+extern "C" int grip_debug_gather_rows(const void* x, const int32_t* row_index, int row_stride, void* out, int n_rows, int d, int four_byte, void* stream) {
+    if (four_byte) return launch_gather_rows4(x, row_index, row_stride, out, n_rows, d, (hipStream_t)stream);
+    return launch_gather_rows((const half_t*)x, row_index, row_stride, (half_t*)out, n_rows, d, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------- backward
