@@ -6,7 +6,8 @@
 // registers into the B operand of the second product, O^T = V^T P^T with the head dims permuted (vt_index_fwd) so that a lane ends with
 // sixteen consecutive output columns.  Input: the packed f32 projection qkv [B*S, 3*H*64] (what the QKV GEMM of a precision-2 tower
 // writes); output: [B*S, H*64] in the split layout of gemm_split.hip (it feeds the out-proj GEMM).  The f32 tower's attention
-// (attention_f32.hip: one thread per query row on the vector ALUs, 2.8 TFLOP/s) was 26 % of a split-tower pass; this is < 3 %.
+// (attention_f32.hip: one thread per query row on the vector ALUs, 2.8 TFLOP/s) was 26 % of a split-tower pass when this kernel replaced it.  On f16-exact weights (two-pass GEMMs) this kernel is itself about a fifth of the tier's kernel time:
+// 0.095 s of the 0.39 s a bench pass spends in the tier (profiles/r06_g_bench_kernel_stats.csv), a larger share since the GEMMs moved to the persistent kernel.
 // S <= 320 (four LDS planes of S x 64 halfs); longer sequences (ViT-L/14@336px) keep the f32 kernel with split output.
 #include <math.h>
 

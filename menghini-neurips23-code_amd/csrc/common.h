@@ -92,6 +92,11 @@ __device__ __forceinline__ void store4(half_t* p, int i, f32x4 v) { ((half4*)p)[
 #ifndef GRIP_SPLIT_LO_SCALE
 #define GRIP_SPLIT_LO_SCALE 1       // lo' = f16((x - hi) * this): 1 = unscaled (single-accumulator kernels; needs unflushed f16 subnormals in the MFMA),
 #endif                              // 2048 = the two-accumulator forms (nothing subnormal where hi is normal)
+// Weight images of the single-accumulator split kernels carry this (exact, power-of-two) factor so that the lo part of a typical |w| ~ 0.02 is a normal
+// f16; bias-initialised accumulators carry it too and every epilogue divides it out (gemm_split.hip; gemm.hip, epilogue_rows_split)
+#define SP1_W_SCALE 256.0f
+// QuickGELU x * sigmoid(1.702 x) on v_exp_f32 + v_rcp_f32 (1 ulp each: far inside the split tier's 2^-22; the f32 tower keeps IEEE exp and division)
+__device__ __forceinline__ float quick_gelu_exact_s(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * x)); }
 struct SplitRow { half_t* p; };
 __device__ __forceinline__ void split_f16x4(f32x4 v, half4& hi, half4& lo) {
     // hi and lo must come from ONE value.  Left to itself (HIP compiles with fp-contract=fast) the compiler fuses the subtraction with the multiply
@@ -182,7 +187,8 @@ struct GemmArgs {
                         // resid + resid_lo (two f16 numbers, ~22 mantissa bits): the epilogue adds both in f32, stores hi = f16(v) to `out` and lo = f16(v - hi) back
                         // to resid_lo (same index as `out`: the stream is updated in place).  The next GEMM still multiplies the hi part alone (one operand
                         // rounding, which does not accumulate); what no longer accumulates is the rounding of the stream itself, 24 of them per ViT-B/16 image
-    int w_exact;        // f32 == 2 only: every element of W is an f16 number (zero lo parts: fp16 checkpoints) -- gemm_split.hip drops the a_hi w_lo product
+    int w_exact;        // f32 == 2 only: every element of W is an f16 number (fp16 checkpoints) AND W is the duplicated image [32 w | 32 w] per line
+                        // (launch_split_dup_weights) -- the a_hi w_lo product is dropped and the GEMM runs as a plain f16 product over 2 K (launch_gemm_split)
     int ablate;         // developer builds only (-DGRIP_ABLATE, tools/mlp_ablation.sh): bit 0 = the c_fc epilogue issues no global store, bit 1 = the K = 4 d
                         // residual GEMM reads its A operand from a 31-MB window (Infinity-Cache resident); timing experiments, results are wrong by design
 };
@@ -196,6 +202,11 @@ int launch_gemm_split(int epi, const GemmArgs& a, hipStream_t s);
 int launch_split_rows(const float* x, void* out, int64_t rows, int K, int64_t ld_in, hipStream_t s, int is_weight = 0, int* overflow_flag = nullptr,
                       int* lo_nonzero_flag = nullptr);   // weights carry gemm_split_weight_scale(); lo_nonzero_flag: set when an element is not an f16 number
 float gemm_split_weight_scale();
+// Weights that are f16 numbers (no lo parts): the image the two-pass GEMMs read is [32 w | 32 w] per line instead of [32 hi | 32 0] -- against an activation row
+// read as f16 [M, 2 K] that is a plain f16 GEMM, which the persistent f16 kernel runs (gemm.hip, launch_gemm_split_k64p).  GemmArgs::w_exact says W is that image.
+bool gemm_split_dup_weights();      // does this build / process use it?  (no: GRIP_SPLIT_WLO=1 forces three passes, and the scaled-lo developer build)
+int launch_split_dup_weights(const void* src, void* dst, int64_t rows, int K, hipStream_t s);      // standard image -> duplicated image (dst may be src)
+int launch_gemm_split_k64p(int epi, const GemmArgs& a, hipStream_t s);
 
 // Activation buffers are f16 (default) or f32 (exact mode): the row kernels take untyped pointers plus the flag.  f32 == 2 (split-f16
 // tier): inputs f32 as in exact mode; launch_layernorm_f16 writes its OUTPUT (a GEMM operand) in the split layout of gemm_split.hip.

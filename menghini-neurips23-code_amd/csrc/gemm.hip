@@ -305,6 +305,71 @@ __device__ __forceinline__ void epilogue_rows(const GemmArgs& g, f32x4 (&acc)[RO
         epilogue_rows_impl<EPI, ROWFRAGS, true, PF, PRE>(g, acc, slab, row0, col0, lane, pre, cb);
 }
 
+// ---- Split-tier form of the 16-row-pass slab epilogue (persistent kernel, EMODE 3: the two-pass GEMMs of the split-f16 tier, launch_gemm_split_k64p).
+// The transposition of epilogue_rows_impl<.., PF = 1> with the tier's types: bias and residual are f32, the output is f32 (EPI_BIAS_F16 included: the
+// tier writes f32 under that id), and EPI_BIAS_GELU_F16 writes the split layout ([32 hi | 32 lo] per 32 columns: it feeds the next split GEMM).  The
+// accumulators carry the weight image's SP1_W_SCALE (the bias they started from included), divided out -- exactly -- on the way into the slab.  A lane owns
+// four consecutive columns of a row: 16 lanes store one row's 256 bytes (f32) or its two 128-byte lines (split layout: 8 bytes into each half).  The lane
+// that stores an element is the one that read its residual, so the residual may be updated in place.
+template <int EPI, bool CHECK>
+__device__ __forceinline__ void epilogue_rows_split_impl(const GemmArgs& g, f32x4 (&acc)[8][4], float* slab, int row0, int col0, int lane) {
+    static_assert(EPI == EPI_F32 || EPI == EPI_BIAS_F16 || EPI == EPI_BIAS_GELU_F16 || EPI == EPI_BIAS_RESID, "epilogue_rows_split: the split tier's four epilogues");
+    constexpr bool RESID = (EPI == EPI_BIAS_RESID);
+    const int frow = lane & 15, fgrp = lane >> 4;
+    const int rr = lane >> 4, cc = (lane & 15) * 4;
+    const int col = col0 + cc;
+    const int ldc = g.ldc;
+    const uint32_t lane_off = (uint32_t)(row0 + rr) * (uint32_t)ldc + (uint32_t)col;      // M * ldc < 2^31 elements (launcher)
+    auto elem_off = [&](int p, int it) -> uint32_t {
+        if constexpr (CHECK) {
+            int row = row0 + p * 16 + it * 4 + rr;
+            row = row < g.M ? row : g.M - 1;
+            return (uint32_t)row * (uint32_t)ldc + (uint32_t)col;
+        } else {
+            return lane_off + (uint32_t)((p * 16 + it * 4) * ldc);
+        }
+    };
+    f32x4 res[2][RESID ? 4 : 1];
+    auto prefetch = [&](int p, int b) {     // all row loads of a pass together, and those of pass p + 1 before the stores of pass p (as epilogue_rows_impl)
+#pragma unroll
+        for (int it = 0; it < 4; ++it) res[b][RESID ? it : 0] = *(const f32x4*)((const float*)g.resid + elem_off(p, it));
+    };
+    if constexpr (RESID) prefetch(0, 0);
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) *(f32x4*)(slab + slab_off<1>(frow, j * 4 + fgrp)) = acc[p][j] * (1.0f / SP1_W_SCALE);
+        if constexpr (RESID)
+            if (p + 1 < 8) prefetch(p + 1, (p + 1) & 1);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const int rl = it * 4 + rr;
+            f32x4 v = *(const f32x4*)(slab + slab_off<1>(rl, lane & 15));
+            const int row = row0 + p * 16 + rl;
+            const uint32_t o = elem_off(p, it);
+            if constexpr (RESID) v += res[p & 1][it];
+            if (!CHECK || row < g.M) {      // rows >= M of A may hold anything (NaN included): their accumulators are never stored
+                if constexpr (EPI == EPI_BIAS_GELU_F16) {
+                    v = (f32x4){quick_gelu_exact_s(v[0]), quick_gelu_exact_s(v[1]), quick_gelu_exact_s(v[2]), quick_gelu_exact_s(v[3])};
+                    store4(SplitRow{(half_t*)g.out + 2 * (size_t)(o - (uint32_t)col)}, col >> 2, v);      // row pitch of the split layout: 2 ldc halfs
+                } else {
+                    *(f32x4*)((float*)g.out + o) = v;
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+template <int EPI>
+__device__ __forceinline__ void epilogue_rows_split(const GemmArgs& g, f32x4 (&acc)[8][4], float* slab, int row0, int col0, int lane) {
+    if (row0 + 128 <= g.M)
+        epilogue_rows_split_impl<EPI, false>(g, acc, slab, row0, col0, lane);
+    else
+        epilogue_rows_split_impl<EPI, true>(g, acc, slab, row0, col0, lane);
+}
+
 // ---- 16-byte-store form of the 16-row-pass epilogue (persistent kernel; the three f16-output epilogues of the pool encode).
 // A lane owns EIGHT consecutive columns of one row: 8 lanes cover the wave tile's 64 columns (one 128-byte line), one wave
 // instruction stores 8 rows x 128 B -- half the store (and residual-load) instructions of the 8-byte form above, whose store tail
@@ -1413,7 +1478,9 @@ __global__ __launch_bounds__(NW * 64) void gemm_k64_kernel(GemmArgs g, int tiles
 // (~2 us of a ~32 us K = 768 tile) nor ends with an idle DMA queue.  The epilogue slabs therefore cannot reuse the stage
 // buffers: they are 16-row, 4 KiB, swizzled slabs in the 32 KiB of LDS beside the two 64 KiB stages.
 // EMODE: 0 = 8-byte-store slab epilogue (every epilogue), 1 = 16-byte-store slab epilogue, 2 = direct epilogue with permuted W
-// fragment rows (1 and 2: the three f16-output epilogues of the pool encode).
+// fragment rows (1 and 2: the three f16-output epilogues of the pool encode), 3 = the split-f16 tier's two-pass GEMMs (form 0's slab with f32 bias /
+// residual / output and the split-layout GELU store; A = activation rows of the split layout read as f16 [M, 2 K], W = the duplicated weight image:
+// one 64-wide K step is one [32 hi | 32 lo] line, its two MFMAs the hi and the lo product -- launch_gemm_split_k64p).
 template <int EPI, int EMODE = 0, bool SD = false>
 __global__ __launch_bounds__(512) void gemm_k64p_kernel(GemmArgs g, int tiles_m, int tiles_n, int colgroup) {
     constexpr int BMT = 256, BNT = 256, NW = 8, WN = 4;
@@ -1576,7 +1643,8 @@ __global__ __launch_bounds__(512) void gemm_k64p_kernel(GemmArgs g, int tiles_m,
         if constexpr (EPI == EPI_BIAS_F16 || EPI == EPI_BIAS_GELU_F16 || EPI == EPI_BIAS_RESID || EPI == EPI_BIAS_RESID_STATS) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const f32x4 b = *(const f32x4*)(g.bias + n0 + wc * 64 + (EMODE == 2 ? (lane >> 4) * 16 + j * 4 : j * 16 + (lane >> 4) * 4));
+                f32x4 b = *(const f32x4*)(g.bias + n0 + wc * 64 + (EMODE == 2 ? (lane >> 4) * 16 + j * 4 : j * 16 + (lane >> 4) * 4));
+                if constexpr (EMODE == 3) b *= SP1_W_SCALE;       // the split tier's weight image carries the factor: so must what the products add to
 #pragma unroll
                 for (int i = 0; i < 8; ++i) acc[i][j] = b;
             }
@@ -1646,7 +1714,9 @@ __global__ __launch_bounds__(512) void gemm_k64p_kernel(GemmArgs g, int tiles_m,
             }
             if constexpr (PRIO1) __builtin_amdgcn_s_setprio(0);
         }
-        if constexpr (EMODE == 4)
+        if constexpr (EMODE == 3)
+            epilogue_rows_split<EPI>(g, acc, slab, m0 + wr * 128, n0 + wc * 64, lane);
+        else if constexpr (EMODE == 4)
             epilogue_rows8h<EPI, true>(g, acc, (half_t*)slab, m0 + wr * 128, n0 + wc * 64, lane, pre);
         else if constexpr (EMODE == 2)
             epilogue_direct<EPI, (EPI == EPI_LNFOLD_F16 || EPI == EPI_LNFOLD_GELU_F16)>(g, acc, m0 + wr * 128, n0 + wc * 64, lane, pre);
@@ -1857,6 +1927,29 @@ static int gemm_cu_count(int* n_cu) {
     }
     *n_cu = (grip_cu_budget() > 0 && grip_cu_budget() < n_cu_dev) ? (grip_cu_budget() & ~7) : n_cu_dev;     // the launch stream owns fewer CUs
     return GRIP_OK;
+}
+
+// The two-pass GEMMs of the split-f16 tier (gemm_split.hip: launch_gemm_split, GemmArgs::w_exact) as plain f16 GEMMs over K' = 2 K on the persistent
+// kernel: the grid and the tile walk are the plan's for that f16 shape; every M takes this one kernel (a row's bits depend on its column panel only).
+int launch_gemm_split_k64p(int epi, const GemmArgs& a_in, hipStream_t s) {
+    GemmShape g{};
+    g.epi = epi; g.M = a_in.M; g.N = a_in.N; g.K = 2 * a_in.K; g.ldc = a_in.ldc; g.m_pad = a_in.m_pad; g.variant = 6;
+    const int rc = gemm_cu_count(&g.n_cu);
+    if (rc) return rc;
+    const GemmPlan p = gemm_plan(g, gemm_tuning());
+    if (p.status) {
+        grip_set_error("%s", p.msg);
+        return p.status;
+    }
+    GemmArgs a = a_in;
+    a.K = g.K;
+    switch (epi) {
+        case EPI_F32: return launch_planned<gemm_k64p_kernel<EPI_F32, 3, true>>(p, a, s, p.colgroup);
+        case EPI_BIAS_F16: return launch_planned<gemm_k64p_kernel<EPI_BIAS_F16, 3, true>>(p, a, s, p.colgroup);
+        case EPI_BIAS_GELU_F16: return launch_planned<gemm_k64p_kernel<EPI_BIAS_GELU_F16, 3, true>>(p, a, s, p.colgroup);
+        case EPI_BIAS_RESID: return launch_planned<gemm_k64p_kernel<EPI_BIAS_RESID, 3, true>>(p, a, s, p.colgroup);
+    }
+    GRIP_REQUIRE(false, "gemm_split: epilogue %d is not part of the split-f16 (inference) path", epi);
 }
 
 static int launch_gemm_impl(int epi, const GemmArgs& a_in, hipStream_t s, int* chosen) {

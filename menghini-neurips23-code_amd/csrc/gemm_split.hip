@@ -22,9 +22,20 @@
 // address and on the ds_read_b128 address: conflict-free).  A lane's MFMA fragment (8 consecutive k of one row) is chunk
 // (lane >> 4) of the row's hi half and chunk 4 + (lane >> 4) of its lo half: one ds_read_b128 each.
 //
-// Kernels: default = 256 x 256 tile, 8 waves as 4 x 2 (64 x 128 per wave), two 64-KiB stages (see `gemm_split1_kernel`); scaled variant =
+// Kernels: default, three passes = 256 x 256 tile, 8 waves as 4 x 2 (64 x 128 per wave), two 64-KiB stages (see `gemm_split1_kernel`); scaled variant =
 // 256 x 128 tile, 8 waves as 4 x 2, K staged 32 wide in a 3-slot ring of 48 KiB stages with counted vmcnt.  Operands are swapped
 // (W fragment first) so a lane ends with four consecutive output columns of one row.
+//
+// TWO PASSES (GemmArgs::w_exact): when every element of W is an f16 number already (its lo part is zero) -- what the block weights of every published CLIP
+// checkpoint are (fp16 archives; the reference's CPU path is clip.load(..., "cpu") = those values cast up, models/clip_encoders.py:108-119) -- the a_hi w_lo
+// product vanishes and acc += a_hi w + a_lo w is a PLAIN f16 GEMM with K doubled: an activation row of the split layout read as f16 is A'[M, 2 K] (row pitch
+// 4 K bytes, one 64-wide K step = one [32 hi | 32 lo] line), and against the duplicated weight image W'[N, 2 K] = [32 w | 32 w] per line
+// (launch_split_dup_weights; grip_tower_finalize builds it in place of [32 hi | 32 0] when the split of the weights left no non-zero lo part) A' W'^T issues
+// the same two v_mfma_f32_16x16x32_f16 per fragment pair, hi then lo, into one f32 accumulator.  So no kernel of this file runs them: launch_gemm_split hands
+// every w_exact launch, of every M, to the persistent f16 kernel (gemm.hip: gemm_k64p_kernel<EPI, 3, true>, launch_gemm_split_k64p -- K pipeline carried
+// across tiles, the next tile's first stages under the epilogue, tuned tile walk and K rotation; its summation order depends on the column panel only, so a
+// row's bits do not depend on the launch it sits in).  Per shape at a refinement chunk (880 x 197 rows; profiles/split_k64p_ab.txt), against the two-pass
+// form of gemm_split1_kernel it replaces (removed): QKV 1.49 -> 1.19 ms, c_fc 1.99 -> 1.54, out-proj 0.60 -> 0.48, c_proj 1.61 -> 1.31.
 #include <math.h>
 
 #include "common.h"
@@ -43,10 +54,7 @@
 #endif
 #define SPL_LO_INV (1.0f / (float)GRIP_SPLIT_LO_SCALE)
 
-// QuickGELU x * sigmoid(1.702 x) on v_exp_f32 + v_rcp_f32 (1 ulp each: far inside this tier's 2^-22; the f32 tower keeps IEEE exp and division)
-__device__ __forceinline__ float quick_gelu_exact_s(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * x)); }
-
-// (hi / lo' of a value: split_f16x4 / store4(SplitRow, ...) in common.h -- the LayerNorm, the f32 attention and the GELU epilogue below
+// (QuickGELU of this tier: quick_gelu_exact_s in common.h; hi / lo' of a value: split_f16x4 / store4(SplitRow, ...) in common.h -- the LayerNorm, the f32 attention and the GELU epilogue below
 // all write the layout through it)
 
 #if GRIP_SPLIT_LO_SCALE != 1
@@ -260,17 +268,13 @@ __global__ __launch_bounds__(512, 2) void gemm_split_kernel(GemmArgs g, int tile
 // order the products need them (the MFMAs trail the reads; the exposed latency is the first read's).
 #define SP1_BM 256
 #define SP1_BN 256
-#define SP1_STAGE_B ((SP1_BM + SP1_BN) * SPL_ROWB)     // 64 KiB
-#define SP1_W_SCALE 256.0f
-// WLO = false (r06, GemmArgs::w_exact): every element of W is an f16 number already (its lo part is zero) -- what the block weights of every
-// published CLIP checkpoint are (fp16 archives; the reference's CPU path is clip.load(..., "cpu") = those values cast up, models/clip_encoders.py:
-// 108-119) -- so the a_hi w_lo product is dropped: two MFMA passes instead of three per fragment pair, the W lo fragments are never read.
-// grip_tower_finalize sets the flag when the split of the weights left no non-zero lo part.
-// Wave layout (r06): the 8 waves as 4 x 2 (64 rows x 128 columns per wave = 4 x 8 fragments), not the f16 kernels' 2 x 4 (128 x 64).  Only the A side needs both
-// of its halves in the two-pass form, so the A side is the short one: 4 a_hi + 4 a_lo + 8 w_hi = 16 fragment reads per K step and wave instead of 20 (three-pass:
-// 24 either way).  An output element's sum does not depend on the wave that forms it (same K order, same pass order): bit-identical to the 2 x 4 layout, whole
-// split tower 10.6k -> 10.95k img/s on fp16-checkpoint weights, 9.35k -> 9.53k otherwise (profiles/r06_split_wave_layout_ab.txt).
-template <int EPI, bool WLO>
+#define SP1_STAGE_B ((SP1_BM + SP1_BN) * SPL_ROWB)     // 64 KiB   (SP1_W_SCALE: common.h)
+// (Weights that are f16 numbers never get here: the two-pass form is a plain f16 GEMM on the persistent kernel -- the header of this file.)
+// Wave layout (r06): the 8 waves as 4 x 2 (64 rows x 128 columns per wave = 4 x 8 fragments), not the f16 kernels' 2 x 4 (128 x 64): 24 fragment reads per K step
+// and wave either way.  An output element's sum does not depend on the wave that forms it (same K order, same pass order): bit-identical to the 2 x 4 layout, whole
+// split tower 9.35k -> 9.53k img/s (profiles/r06_split_wave_layout_ab.txt; the layout was chosen for the two-pass form this kernel used to have, whose A side
+// alone needed both halves).
+template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_split1_kernel(GemmArgs g, int tiles_m, int tiles_n) {
     constexpr int FI = 4, FJ = 8;          // A / W fragments (16 rows each) per wave
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -326,7 +330,7 @@ __global__ __launch_bounds__(512, 2) void gemm_split1_kernel(GemmArgs g, int til
         __builtin_amdgcn_s_barrier();                         // stage kt visible; the other slot fully read
         const char* st = lds + (kt & 1) * SP1_STAGE_B;
         half8 ah[FI], al[FI], wh[FJ], wl[FJ];
-        // The hi fragments (12 reads) go out first; the lo reads (12, two-pass: the A side's 8 / 4) follow BETWEEN the first 24 MFMAs, which only need
+        // The hi fragments (12 reads) go out first; the 12 lo reads follow BETWEEN the first 24 MFMAs, which only need
         // hi operands.  (All 24 up front would exceed the 4-bit lgkmcnt: the compiler then waits for every read before the first product -- 192
         // ds_read_b128 per workgroup and K step in front of idle matrix pipes.)
         wh[0] = *(const half8*)(st + b_row + swz_hi);
@@ -335,21 +339,21 @@ __global__ __launch_bounds__(512, 2) void gemm_split1_kernel(GemmArgs g, int til
 #pragma unroll
         for (int j = 1; j < FJ; ++j) wh[j] = *(const half8*)(st + b_row + j * 16 * SPL_ROWB + swz_hi);
         __builtin_amdgcn_sched_barrier(0);
-        // stage kt + 1 into the other slot, one piece after every twelfth (WLO: eighth) MFMA (past the end: a valid slice into a slot nobody reads)
+        // stage kt + 1 into the other slot, one piece after every twelfth MFMA (past the end: a valid slice into a slot nobody reads)
         char* abase = lds + ((kt + 1) & 1) * SP1_STAGE_B + wave * 32 * SPL_ROWB;
         char* bbase = lds + ((kt + 1) & 1) * SP1_STAGE_B + SP1_BM * SPL_ROWB + wave * 32 * SPL_ROWB;
         const char* as = a_src + (size_t)ks_stage * SPL_ROWB;
         const char* ws = w_src + (size_t)ks_stage * SPL_ROWB;
         ks_stage = next_slice(ks_stage);
-        constexpr int NQ = WLO ? 96 : 64, PIECE_EVERY = NQ / 8, LO_READS = WLO ? 12 : FI;
+        constexpr int NQ = 96, PIECE_EVERY = NQ / 8, LO_READS = 12;
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) {        // passes over the 32 fragment pairs (j-major): w_hi a_hi, [w_lo a_hi,] w_hi a_lo
+        for (int q = 0; q < NQ; ++q) {        // passes over the 32 fragment pairs (j-major): w_hi a_hi, w_lo a_hi, w_hi a_lo
             const int pass = q >> 5, j = ((q & 31) / FI), i = q % FI;
             if (pass == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], ah[i], acc[i][j], 0, 0, 0);
-            else if (WLO && pass == 1) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[j], ah[i], acc[i][j], 0, 0, 0);
+            else if (pass == 1) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[j], ah[i], acc[i][j], 0, 0, 0);
             else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], al[i], acc[i][j], 0, 0, 0);
-            if (q < 2 * LO_READS && !(q & 1)) {         // a lo read after every other MFMA of the first pass: [the w_lo fragments, then] the a_lo fragments
-                const int r = (q >> 1) + (WLO ? 0 : FJ);
+            if (q < 2 * LO_READS && !(q & 1)) {         // a lo read after every other MFMA of the first pass: the w_lo fragments, then the a_lo fragments
+                const int r = q >> 1;
                 if (r < FJ) wl[r] = *(const half8*)(st + b_row + r * 16 * SPL_ROWB + swz_lo);
                 else al[r - FJ] = *(const half8*)(st + a_row + (r - FJ) * 16 * SPL_ROWB + swz_lo);
                 __builtin_amdgcn_sched_barrier(0);
@@ -412,6 +416,36 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict
     store4(SplitRow{out + r * 2 * (int64_t)K}, c >> 2, v);
 }
 
+// Standard weight image [32 hi | 32 lo] -> the duplicated image [32 hi | 32 hi] of f16-exact weights (every lo is zero there).  One thread per 16 bytes of a
+// hi half; dst may be src (a thread reads what it alone writes).
+__global__ __launch_bounds__(256) void split_dup_weights_kernel(const half_t* src, half_t* dst, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t o = (i >> 2) * 64 + (i & 3) * 8;
+    const half8 v = *(const half8*)(src + o);
+    *(half8*)(dst + o) = v;
+    *(half8*)(dst + o + 32) = v;
+}
+
+int launch_split_dup_weights(const void* src, void* dst, int64_t rows, int K, hipStream_t s) {
+    GRIP_REQUIRE(K % 32 == 0 && rows > 0, "split_dup_weights: need K %% 32 == 0 (rows=%lld K=%d)", (long long)rows, K);
+    const int64_t n = rows * (K / 8);
+    hipLaunchKernelGGL(split_dup_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const half_t*)src, (half_t*)dst, n);
+    GRIP_CHECK_HIP(hipGetLastError());
+    return GRIP_OK;
+}
+
+// GRIP_SPLIT_WLO=1 (developer switch: always form the a_hi w_lo product) is honoured where the weight image is made: the three-pass kernel needs the
+// standard image, so f16-exact weights then keep it and no launch is ever marked w_exact.
+bool gemm_split_dup_weights() {
+#if GRIP_SPLIT_LO_SCALE == 1
+    static const bool force_wlo = getenv("GRIP_SPLIT_WLO") && atoi(getenv("GRIP_SPLIT_WLO")) == 1;
+    return !force_wlo;
+#else
+    return false;
+#endif
+}
+
 float gemm_split_weight_scale() {
 #if GRIP_SPLIT_LO_SCALE == 1
     return SP1_W_SCALE;
@@ -439,31 +473,37 @@ int launch_gemm_split(int epi, const GemmArgs& a, hipStream_t s) {
 #if GRIP_SPLIT_LO_SCALE == 1
     constexpr int BM = SP1_BM, BN = SP1_BN;
     constexpr size_t lds = (size_t)2 * SP1_STAGE_B;
-#define GRIP_SPLIT_KERNEL(E, WLO) gemm_split1_kernel<E, WLO>
+#define GRIP_SPLIT_KERNEL(E) gemm_split1_kernel<E>
 #else
     constexpr int BM = SPL_BM, BN = SPL_BN;
     constexpr size_t lds = (size_t)SPL_NST * SPL_STAGE_B;
-#define GRIP_SPLIT_KERNEL(E, WLO) gemm_split_kernel<E>
+#define GRIP_SPLIT_KERNEL(E) gemm_split_kernel<E>
 #endif
     GRIP_REQUIRE(a.N % BN == 0, "gemm_split: need N %% %d == 0 (N=%d)", BN, a.N);
-    static const bool force_wlo = getenv("GRIP_SPLIT_WLO") && atoi(getenv("GRIP_SPLIT_WLO")) == 1;      // developer A/B: always form the a_hi w_lo product
-    const bool wlo = !a.w_exact || force_wlo;
+    const bool wlo = !a.w_exact;
     g_last_wlo = wlo;
+#if GRIP_SPLIT_LO_SCALE == 1
+    // Two passes (W is the duplicated image of f16-exact weights): the plain f16 GEMM over 2 K on the persistent kernel, for every M and every shape -- the
+    // two kernel families initialise and rotate differently, and a row's bits must not depend on the launch it sits in.
+    if (!wlo) return launch_gemm_split_k64p(epi, a, s);
+#else
+    GRIP_REQUIRE(wlo, "gemm_split: the scaled-lo build has no two-pass form (GemmArgs::w_exact must be 0)");
+#endif
     const int tiles_m = (a.M + BM - 1) / BM, tiles_n = a.N / BN;
     GRIP_REQUIRE(a.m_pad >= (int64_t)tiles_m * BM, "gemm_split: A must be allocated up to the 256-row tile (M=%d m_pad=%lld)", a.M, (long long)a.m_pad);
     dim3 grid(tiles_m * tiles_n), block(512);
-#define GRIP_GEMM_LAUNCH(E, WLO)                                                                                            \
+#define GRIP_GEMM_LAUNCH(E)                                                                                                 \
     {                                                                                                                       \
         static bool configured = false;                                                                                     \
         if (!configured) {                                                                                                  \
-            GRIP_CHECK_HIP(hipFuncSetAttribute((const void*)GRIP_SPLIT_KERNEL(E, WLO), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            GRIP_CHECK_HIP(hipFuncSetAttribute((const void*)GRIP_SPLIT_KERNEL(E), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
             configured = true;                                                                                              \
         }                                                                                                                   \
-        hipLaunchKernelGGL((GRIP_SPLIT_KERNEL(E, WLO)), grid, block, lds, s, a, tiles_m, tiles_n);                          \
+        hipLaunchKernelGGL((GRIP_SPLIT_KERNEL(E)), grid, block, lds, s, a, tiles_m, tiles_n);                               \
     }
 #define GRIP_GEMM_CASE(E)                                                                                                   \
     case E:                                                                                                                 \
-        if (wlo) GRIP_GEMM_LAUNCH(E, true) else GRIP_GEMM_LAUNCH(E, false)                                                  \
+        GRIP_GEMM_LAUNCH(E)                                                                                                 \
         break;
     switch (epi) {
         GRIP_GEMM_CASE(EPI_F32)

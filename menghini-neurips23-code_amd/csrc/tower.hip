@@ -234,7 +234,7 @@ struct grip_tower {
     half_t* w16;      // GEMM-operand blob: f16, or f32 when f32 != 0 (exact mode) -- always addressed through wop()
     float* w32;
     int f32 = 0;      // dims.precision != 0: activations, residual stream, attention and the operand blob's primary slots are f32 (inference only)
-    int w_exact = 0;  // precision 2: no block weight has a non-zero lo part (set by grip_tower_finalize; GemmArgs::w_exact)
+    int w_exact = 0;  // precision 2: no block weight has a non-zero lo part and the split images are the duplicated ones (set by grip_tower_finalize; GemmArgs::w_exact)
     int split = 0;    // dims.precision == 2: the four GEMMs of a block run on the split-f16 kernel (gemm_split.hip); their A operands are written in
                       // its layout by the producers (LayerNorm, f32 attention, GELU epilogue), their weights by grip_tower_finalize (#S slots)
     uint64_t generation = 0;   // counts train-mode forwards (see `pending`)
@@ -420,10 +420,19 @@ extern "C" int grip_tower_finalize(grip_tower* t, void* stream) {
         int flags[2] = {0, 0};
         if (!rc && (hipMemcpyAsync(flags, flag, 2 * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)) rc = GRIP_ERR_HIP;
         const int over = flags[0];
-        t->w_exact = flags[1] == 0;         // fp16 checkpoints: no block weight needs its lo part (GemmArgs::w_exact)
+        // fp16 checkpoints: no block weight needs its lo part -- the images become [32 w | 32 w] lines in place and the block GEMMs run as plain f16 GEMMs
+        // over 2 K (GemmArgs::w_exact).  GRIP_SPLIT_WLO=1 keeps the standard images and with them the three-pass kernel.
+        t->w_exact = flags[1] == 0 && gemm_split_dup_weights();
         (void)hipFree(flag);
         if (rc == GRIP_ERR_HIP) { grip_set_error("tower_finalize: HIP error while splitting the weights"); return rc; }
         if (rc) return rc;
+        if (t->w_exact)
+            for (const LayerW& w : t->L.layer) {
+                if ((rc = launch_split_dup_weights(t->wop(w.in_wS), t->wop(w.in_wS), 3 * d, d, s))) return rc;
+                if ((rc = launch_split_dup_weights(t->wop(w.out_wS), t->wop(w.out_wS), d, d, s))) return rc;
+                if ((rc = launch_split_dup_weights(t->wop(w.fc_wS), t->wop(w.fc_wS), 4 * d, d, s))) return rc;
+                if ((rc = launch_split_dup_weights(t->wop(w.proj_wS), t->wop(w.proj_wS), d, 4 * d, s))) return rc;
+            }
         GRIP_REQUIRE(!over, "tower_finalize: a block weight times %g leaves the f16 range (or is not finite): split-f16 towers (precision 2) need |w| < %g",
                      (double)gemm_split_weight_scale(), 65504.0 / (double)gemm_split_weight_scale());
     }
@@ -830,9 +839,18 @@ extern "C" int grip_debug_gemm_split(int epi, const float* A, const float* W, in
     (void)hipFree(flag);
     if (rc) return rc;
     GemmArgs a{};
-    a.w_exact = !inexact;
+    a.w_exact = !inexact && gemm_split_dup_weights();
     a.f32 = 2; a.A = a_split; a.W = w_split; a.M = M; a.N = N; a.K = K; a.m_pad = m_pad; a.bias = bias; a.resid = resid; a.out = out; a.ldc = N;
-    return launch_gemm(epi, a, s);
+    if (!a.w_exact) return launch_gemm(epi, a, s);
+    // f16-exact W: the GEMM reads the duplicated image, built in scratch of this call's own (w_split keeps the standard layout for the caller)
+    void* w_dup = nullptr;
+    GRIP_CHECK_HIP(hipMalloc(&w_dup, (size_t)N * K * 4));
+    a.W = w_dup;
+    rc = launch_split_dup_weights(w_split, w_dup, N, K, s);
+    if (!rc) rc = launch_gemm(epi, a, s);
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) { grip_set_error("debug_gemm_split: HIP error"); rc = GRIP_ERR_HIP; }
+    (void)hipFree(w_dup);
+    return rc;
 }
 int gemm_split_last_wlo();
 extern "C" int grip_debug_split_last_wlo(void) { return gemm_split_last_wlo(); }
