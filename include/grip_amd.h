@@ -325,6 +325,28 @@ int grip_cache_head_backward(const float* img_emb, const float* keys, const int3
                              void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 9 additions) Feature adapter (CLIP-Adapter; models/adapter_models.py ClipAdapterModel; csrc/feature_adapter.hip): a bias-free bottleneck MLP on
+ * the image embedding, blended back into it.  All tensors f32 on the device and 16-byte aligned.
+ *   img_emb  [n, e]   image embeddings, NOT normalised (the tower's output; grip_cosine_head normalises what this returns)
+ *   w1 [h, e], w2 [e, h]   the two bias-free layers in nn.Linear layout
+ *   forward:  out[n, e] = ratio * ReLU(ReLU(img_emb w1^T) w2^T) + (1 - ratio) * img_emb, ONE launch; the hidden activations stay in LDS.
+ *             hidden_out [n, h] / act_out [n, e]: both NULL (inference) or both given (training): the post-ReLU hidden and the post-ReLU x, all the
+ *             backward needs.  out must not alias img_emb.  ratio = 0 returns img_emb and ratio = 1 returns x, bit for bit.
+ *   backward: dX = ratio * grad_out o [act > 0];  grad_w2 = dX^T hidden;  dH = (dX w2) o [hidden > 0];  grad_w1 = dH^T img_emb -- written, not
+ *             accumulated; a pure function of its arguments (it needs no forward before it; the masks are read from hidden / act, strictly > 0).
+ *             Two launches.  (No gradient to img_emb: the image tower of the strategies that use the head is frozen.)
+ *   e a multiple of 64, 64 .. 1024; h a multiple of 16, 16 .. 256; n >= 1.  The products run on the f32 MFMA; no atomics, one writer per element,
+ *   every element one chain in a fixed order (the rows of a gradient in ascending order): bit-reproducible, and the bits of a forward row do not
+ *   depend on n, on the row's place in a tile or on the call the row is in.
+ *   workspace (backward only): grip_feature_adapter_workspace bytes = n * h * 4 + 256 (dH and alignment slack): it holds NO e * h partial,
+ *   whatever n is.  The workspace call needs no device. */
+int grip_feature_adapter_workspace(int n, int e, int h, size_t* bytes);
+int grip_feature_adapter_forward(const float* img_emb, const float* w1, const float* w2, float ratio, int n, int e, int h, float* out, float* hidden_out,
+                                 float* act_out, void* stream);
+int grip_feature_adapter_backward(const float* img_emb, const float* w2, const float* hidden, const float* act, const float* grad_out, float ratio, int n,
+                                  int e, int h, float* grad_w1, float* grad_w2, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CLIP preprocessing of one decoded image: the `_transform` the reference applies per item on the host
  * (data/dataset.py:64-79 via clip.load's preprocess): Resize(n_px, BICUBIC) -> CenterCrop(n_px) -> ToTensor -> Normalize.
  * Bit-exact with Pillow's 8-bit bicubic resample; only the cropped rows / columns are produced.

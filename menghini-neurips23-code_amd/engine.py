@@ -768,6 +768,66 @@ class CacheHeadFn(torch.autograd.Function):
         return None, gk, None, None, None, None, (grad_out.to(ldtype) if need_l else None)
 
 
+def _feature_adapter_args(img_emb, w1, w2):
+    """Contiguous f32 operands and (n, e, h) of a feature-adapter call, shapes checked (the kernel checks the values of e and h)."""
+    img, a, b = img_emb.detach().contiguous().float(), w1.detach().contiguous().float(), w2.detach().contiguous().float()
+    if img.dim() != 2 or a.dim() != 2 or b.dim() != 2 or a.shape[1] != img.shape[1] or tuple(b.shape) != (a.shape[1], a.shape[0]):
+        raise native.GripError(f"feature adapter: img_emb {tuple(img_emb.shape)}, w1 {tuple(w1.shape)}, w2 {tuple(w2.shape)}: expected [n, e], [h, e], [e, h]")
+    return img, a, b, (img.shape[0], img.shape[1], a.shape[0])
+
+
+def _feature_adapter_workspace(dims, device):
+    nbytes = c_size_t()
+    native.check(native.lib().grip_feature_adapter_workspace(*dims, byref(nbytes)))
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+
+def _feature_adapter_forward(img_emb, w1, w2, ratio, train):
+    img, a, b, dims = _feature_adapter_args(img_emb, w1, w2)
+    out = torch.empty_like(img)
+    hidden = torch.empty(dims[0], dims[2], dtype=torch.float32, device=img.device) if train else None
+    act = torch.empty_like(img) if train else None
+    native.check(native.lib().grip_feature_adapter_forward(_ptr(img), _ptr(a), _ptr(b), float(ratio), *dims, _ptr(out), _ptr(hidden), _ptr(act), _stream()))
+    return out, hidden, act, img, a, b, dims
+
+
+def feature_adapter(img_emb, w1, w2, ratio):
+    """CLIP-Adapter's feature head on the native kernel (csrc/feature_adapter.hip), no autograd, one launch:
+    out [n, e] = ratio * relu(relu(img_emb @ w1.T) @ w2.T) + (1 - ratio) * img_emb, f32.  A row's bits depend on that row and the weights only."""
+    return _feature_adapter_forward(img_emb, w1, w2, ratio, False)[0]
+
+
+class FeatureAdapterFn(torch.autograd.Function):
+    """(img_emb, w1, w2, ratio) -> adapted features, native forward and backward.  The gradient goes to w1 and w2; the image embeddings come from a
+    frozen tower and get none -- marking them as requiring grad is an error, not a silent zero.  When neither weight requires grad the forward is the
+    inference call (the hidden activations never reach memory); otherwise it keeps the two post-ReLU tensors for the backward."""
+
+    @staticmethod
+    def forward(ctx, img_emb, w1, w2, ratio):
+        if img_emb.requires_grad:
+            raise native.GripError("feature adapter: img_emb requires grad, but the head has no gradient for the image embeddings (its image tower is "
+                                   "frozen); detach them")
+        train = w1.requires_grad or w2.requires_grad
+        out, hidden, act, img, a, b, dims = _feature_adapter_forward(img_emb, w1, w2, ratio, train)
+        if train:
+            ctx.save_for_backward(img, b, hidden, act)
+        ctx.ratio, ctx.dims = float(ratio), dims
+        ctx.meta = ((w1.shape, w1.dtype, w1.requires_grad), (w2.shape, w2.dtype, w2.requires_grad))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        img, b, hidden, act = ctx.saved_tensors
+        n, e, h = ctx.dims
+        g = grad_out.contiguous().float()
+        g1, g2 = torch.empty(h, e, dtype=torch.float32, device=img.device), torch.empty(e, h, dtype=torch.float32, device=img.device)
+        ws = _feature_adapter_workspace(ctx.dims, img.device)
+        native.check(native.lib().grip_feature_adapter_backward(_ptr(img), _ptr(b), _ptr(hidden), _ptr(act), _ptr(g), ctx.ratio, n, e, h, _ptr(g1), _ptr(g2),
+                                                                _ptr(ws), ws.numel(), _stream()))
+        (s1, d1, need1), (s2, d2, need2) = ctx.meta
+        return None, (g1.reshape(s1).to(d1) if need1 else None), (g2.reshape(s2).to(d2) if need2 else None), None
+
+
 def leaderboard_scan(probs, pred, path_rank, k):
     """Host scan (exact, sequential).  probs [n,c] f32 CPU, pred [n] int32 CPU, path_rank [n] int64 CPU."""
     import numpy as np

@@ -19,7 +19,7 @@ import torch
 
 from .. import clip, dist as gdist, pseudolabels as pl, steps
 from ..engine import cosine_head
-from ..models import CustomImageEncoder, CustomTextEncoder, ImagePrefixModel, MaPLeModel, TextPrefixModel, TipAdapterModel, UPTModel
+from ..models import ClipAdapterModel, CustomImageEncoder, CustomTextEncoder, ImagePrefixModel, MaPLeModel, TextPrefixModel, TipAdapterModel, UPTModel
 from ..utils import pseudolabel_top_k
 
 log = logging.getLogger(__name__)
@@ -62,6 +62,12 @@ class TrainingStrategy:
         self.tip, self.tip_classes, self.tip_losses, self.tip_search = None, None, [], None
         if bool(getattr(config, "TIP_ADAPTER", False)) and self.modality != "text":
             log.info(f"TIP_ADAPTER is ignored by the {self.modality} strategies: their pool features move with the prompt (textual strategies only)")
+        # CLIP_ADAPTER (textual strategies): the feature adapter trained on the cached training features after each prompt training
+        # (build_feature_adapter); None = off
+        self.adapter, self.adapter_losses = None, []
+        if bool(getattr(config, "CLIP_ADAPTER", False)) and self.modality != "text":
+            log.info(f"CLIP_ADAPTER is ignored by the {self.modality} strategies: their image features move with the prompt (textual strategies only)")
+        self.clip_adapter()      # (raises when CLIP_ADAPTER and TIP_ADAPTER are both set)
         self.declare_custom_encoder()
         self.initialize_prompts_parameters()
 
@@ -135,9 +141,20 @@ class TrainingStrategy:
         the cache costs no tower pass.  Visual and multimodal strategies ignore it, as they ignore COOP_DEEP."""
         return self.modality == "text" and bool(getattr(self.config, "TIP_ADAPTER", False))
 
+    def clip_adapter(self):
+        """CLIP-Adapter feature head for the textual strategies: config CLIP_ADAPTER, default False (ADAPTER_RATIO 0.2, ADAPTER_REDUCTION 4,
+        ADAPTER_EPOCHS 20, ADAPTER_LR 1e-3).  Their image tower is frozen and their training features are cached, so the adapter trains without a
+        tower pass.  Visual and multimodal strategies ignore it, as they ignore TIP_ADAPTER.  Together with TIP_ADAPTER it is refused: they are two
+        different heads on the same features, and stacking them is not defined here."""
+        on = self.modality == "text" and bool(getattr(self.config, "CLIP_ADAPTER", False))
+        if on and bool(getattr(self.config, "TIP_ADAPTER", False)):
+            raise ValueError("CLIP_ADAPTER and TIP_ADAPTER are two different heads on the same image features: set one of them")
+        return on
+
     def define_model(self, classes=None):
         c, dev = self.config, self.device
         self.tip = None      # a cache belongs to the prompt it was built after: validation during the next training sees CLIP logits alone
+        self.adapter = None  # and so does a feature adapter
         classes = classes if classes is not None else self.classes
         if self.modality == "text":
             deep = getattr(self, "initial_deep_prefix", None)
@@ -420,6 +437,8 @@ class TrainingStrategy:
         for batch in self._loader(data, False):
             img = batch[0].to(self.device)
             image_features, text_features = self.features(img, classes)
+            if self.adapter is not None:      # CLIP_ADAPTER: the features are adapted before the head (row by row: the batching changes no bit)
+                image_features = self.adapter(image_features)
             logits, _, am, _ = cosine_head(image_features, text_features, self.scale(), want_probs=False)
             if self.tip is not None:      # TIP_ADAPTER: the cache term of the iteration's training set
                 logits = self._add_cache_term(image_features, logits, classes)
@@ -447,6 +466,8 @@ class TrainingStrategy:
                 best_acc, best_prompt = val_acc, self.prompt_snapshot()
         if self.tip_adapter():
             self.build_tip_cache(train_data, val_data, only_seen=only_seen)
+        if self.clip_adapter():
+            self.build_feature_adapter(train_data, val_data, only_seen=only_seen)
         return best_acc, best_prompt
 
     # ------------------------------------------------------------------ Tip-Adapter cache (TIP_ADAPTER, textual strategies)
@@ -530,6 +551,53 @@ class TrainingStrategy:
             dst, src = (torch.tensor(x, device=logits.device) for x in zip(*cols))
             logits[:, dst] += term[:, src]
         return logits
+
+    # ------------------------------------------------------------------ CLIP-Adapter feature head (CLIP_ADAPTER, textual strategies)
+    def build_feature_adapter(self, train_data, val_data=None, only_seen=False):
+        """The CLIP-Adapter of the iteration just trained: a fresh models.ClipAdapterModel (seeded with OPTIM_SEED from a generator of its own)
+        trained for ADAPTER_EPOCHS on the training set's cached frozen features (labelled shots and pseudolabelled pool rows: the rows the prompt
+        steps read) against the fixed text features of the prompt just trained, with the strategy's row weights, a LOADER_SEED permutation per
+        epoch and batches of BATCH_SIZE (steps.GraphedAdapterStep, or steps.adapter_step with GRAPH_STEPS: False; AdamW at ADAPTER_LR).  From here
+        on predict() -- hence _run_validation, test_predictions and evaluation -- adapts the image features before the cosine head.
+
+        The pseudolabel pass is NOT touched: assign_pseudo_labels and the frozen-CLIP pass keep ranking the pool by the CLIP logits of the prompts
+        alone, so pseudolabel lists and prompt files are the same with the switch on or off."""
+        c = self.config
+        classes, ids, lut = self._class_space(only_seen)
+        with torch.random.fork_rng(devices=[]):      # (a DataLoader without a generator of its own draws its base seed from the GLOBAL stream, which
+            feats, _, labs, names = self._tip_inputs(train_data, classes, lut)      # the GRIP prompt re-initialisations read: ADVICE r5 -- left as found)
+        with torch.no_grad():
+            text = self.model(classes).detach().float().contiguous()
+        model = ClipAdapterModel(feats.shape[1], reduction=int(getattr(c, "ADAPTER_REDUCTION", 4)), ratio=float(getattr(c, "ADAPTER_RATIO", 0.2)),
+                                 seed=int(getattr(c, "OPTIM_SEED", 0)), device=self.device)
+        epochs, B, scale = int(getattr(c, "ADAPTER_EPOCHS", 20)), int(c.BATCH_SIZE), self.scale()
+        opt = torch.optim.AdamW([model.w1, model.w2], lr=float(getattr(c, "ADAPTER_LR", 1e-3)), eps=1e-4)
+        step = steps.GraphedAdapterStep(model, text, scale, opt) if getattr(c, "GRAPH_STEPS", True) else None
+        g = torch.Generator().manual_seed(int(getattr(c, "LOADER_SEED", 0)))
+        gid = ids[labs].tolist()      # global label ids, as row_weights reads them
+        self.adapter_losses = []
+        for _ in range(epochs):
+            order = torch.randperm(len(names), generator=g).tolist()
+            total, nb = torch.zeros((), dtype=torch.float64, device=self.device), 0
+            for lo in range(0, len(order), B):
+                rows = order[lo:lo + B]
+                idx = torch.tensor(rows, device=self.device)
+                w = self.row_weights([gid[r] for r in rows], [names[r] for r in rows]).to(self.device)
+                if step is not None:
+                    total += step(feats[idx], labs[idx], w)
+                else:
+                    total += steps.adapter_step(model, feats[idx], text, scale, labs[idx].to(torch.int32), w, opt)
+                nb += 1
+            self.adapter_losses.append(float(total) / max(nb, 1))
+        if epochs > 0:
+            log.info(f"CLIP-Adapter: {epochs} epochs over {len(names)} rows, loss {self.adapter_losses[0]:.4f} -> {self.adapter_losses[-1]:.4f}")
+        self.adapter = model
+        return model
+
+    def load_feature_adapter(self, path):
+        """Install an adapter file written by utils.save_parameters(..., adapter=strategy.adapter)."""
+        self.adapter = ClipAdapterModel.load(path, device=self.device)
+        return self.adapter
 
     # ------------------------------------------------------------------ evaluation
     def test_predictions(self, data, standard_zsl=False):
@@ -655,7 +723,7 @@ class TrainingStrategy:
             out = self.train(data, val_data, only_seen=only_seen, iter_train=True)
             from ..utils import save_parameters, save_pseudo_labels
             save_pseudo_labels(list(data.filepaths), list(data.labels), c, niter)     # compute_metrics.py:150-154
-            save_parameters(out[1], c, iteration=niter, cache=self.tip)
+            save_parameters(out[1], c, iteration=niter, cache=self.tip, adapter=self.adapter)
             log.info(f"GRIP iteration {niter}/{num_iter}: {c.N_PSEUDOSHOTS} pseudo-shots per class, val acc {out[0]:.3f}")
         return out
 

@@ -88,6 +88,11 @@ _SIGS = {
                                         c_void_p]),
     "grip_cache_head_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                          c_size_t, c_void_p]),
+    # (ABI 9 additions) feature adapter (CLIP-Adapter): out = ratio * ReLU(ReLU(f W1^T) W2^T) + (1 - ratio) * f (csrc/feature_adapter.hip)
+    "grip_feature_adapter_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "grip_feature_adapter_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "grip_feature_adapter_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                              c_size_t, c_void_p]),
     "grip_preprocess_image": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                       c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "grip_preprocess_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -398,3 +398,32 @@ class GraphedTipStep(GraphedStep):
         else:
             self.z.copy_(clip_logits)
         return super().__call__(feats, labels, row_weight)
+
+
+def adapter_step(model, image_features, text_features, scale, labels, row_weight, optimizer, return_logits=False):
+    """CLIP-Adapter step on a models.ClipAdapterModel: feature adapter over cached image features -> cosine head against the fixed text features of
+    the trained prompt (constants of the step) -> weighted CE -> the gradients of w1 and w2 -> optimizer.  No tower runs."""
+    feats = model(image_features)
+    logits = CosineHeadFn.apply(feats, text_features, scale)
+    loss = WeightedCEFn.apply(logits, labels, row_weight)
+    return _finish(loss, [model.w1, model.w2], optimizer, logits if return_logits else None)
+
+
+class GraphedAdapterStep(GraphedStep):
+    """adapter_step replayed from a HIP graph: the adapter's forward and backward, the cosine head's and the loss are a handful of kernels, so a
+    step is launch cost and little else.  The static input is the feature block [B, embed_dim] (GraphedStep's `x`); the text features and the scale
+    are constants of the object.  A batch of another shape runs the eager step."""
+
+    def __init__(self, model, text_features, scale, optimizer):
+        super().__init__(optimizer)
+        self.model, self.scale = model, float(scale)
+        self.text = text_features.detach().float().contiguous()
+
+    def params(self):
+        return [self.model.w1, self.model.w2]
+
+    def forward_logits(self):
+        return CosineHeadFn.apply(self.model(self.x), self.text, self.scale)
+
+    def eager(self, feats, labels, row_weight):
+        return adapter_step(self.model, feats, self.text, self.scale, labels, row_weight, self.optimizer, return_logits=True)
