@@ -347,6 +347,37 @@ int grip_feature_adapter_backward(const float* img_emb, const float* w2, const f
                                   int e, int h, float* grad_w1, float* grad_w2, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 9 additions) Transductive label propagation over a pool (pseudolabels.LabelPropagation; csrc/knn_graph.hip): a kNN graph of image
+ * embeddings and a random walk of class probabilities over it.  All tensors f32 / int32 on the device; queries, base and out 16-byte aligned.
+ *
+ * grip_knn_graph: row i of idx_out / sim_out [n, k] lists the k rows j of `base` with the largest cosine s_ij = (q_i . x_j) / (|q_i| |x_j|), under
+ * the TOTAL order (sim descending, then index ascending), written in that order.
+ *   queries [n, e], base [m, e]   embeddings, NOT normalised (as grip_cosine_head takes them): the reciprocal norms scale the score
+ *   self_offset   >= 0: query i IS base row self_offset + i and that row is excluded for it (pool on pool: queries == base, 0; a window of the
+ *                 base: queries == base + self_offset * e -- the norms are then computed once); -1: nothing is excluded
+ *   e a multiple of 4 up to 2048; 1 <= k <= 32; n, m >= 1; m - (self_offset >= 0) >= k; with self_offset >= 0, self_offset + n <= m.
+ *   Finite rows of non-zero norm are the CALLER's duty (device data): a NaN or a zero row makes the lists of the rows that meet it meaningless.
+ *   The products run on the f32 MFMA and the [n, m] scores never reach memory; no atomics.  A score is one MFMA chain over e in ascending order (an
+ *   fmaf chain) times the two reciprocal norms, so the idx / sim bits of a query row depend on that row and the base only -- not on n, on the row's
+ *   place in a tile or on the call -- and bit-identical base rows tie, the lower index first.
+ *   workspace: grip_knn_graph_workspace bytes (the reciprocal norms and, with few query rows, the per-share lists that a second launch merges under
+ *   the same total order).  The workspace call needs no device.
+ *
+ * grip_label_propagate: random-walk propagation on the DIRECTED kNN graph (idx refers to rows of the same set: values in [0, n) are the caller's duty)
+ *   w_ik = exp(gamma (sim_ik - sim_i0)) / sum_k' exp(gamma (sim_ik' - sim_i0))        (sim_i0: the row's first = largest entry)
+ *   Z^0 = probs,  Z^{t+1}_i = fmaf(alpha, sum_k w_ik Z^t_{idx_ik}, (1 - alpha) probs_i),  t = 0 .. iters - 1;  out = Z^iters
+ *   probs, out [n, c]; idx, sim [n, k]; argmax_out [n] int32 or NULL: the first index of the maximum of out's row.  The k neighbours are added in
+ *   list order; alpha = 0 returns probs bit for bit.  0 <= alpha < 1, gamma >= 0, iters >= 1, 1 <= k <= 32, any c >= 1; out must not alias probs.
+ *   One call enqueues the weights and the `iters` steps, ping-ponging between out and the workspace (grip_label_propagate_workspace bytes).
+ *   This is NOT ZLaP's symmetrised, conjugate-gradient-solved system: no class (text) nodes, no symmetrisation, no convergence test. */
+int grip_knn_graph_workspace(int n, int m, int e, int k, size_t* bytes);
+int grip_knn_graph(const float* queries, const float* base, int n, int m, int e, int k, int self_offset, int32_t* idx_out, float* sim_out,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int grip_label_propagate_workspace(int n, int c, int k, size_t* bytes);
+int grip_label_propagate(const float* probs, const int32_t* idx, const float* sim, float alpha, float gamma, int iters, int n, int c, int k,
+                         float* out, int32_t* argmax_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CLIP preprocessing of one decoded image: the `_transform` the reference applies per item on the host
  * (data/dataset.py:64-79 via clip.load's preprocess): Resize(n_px, BICUBIC) -> CenterCrop(n_px) -> ToTensor -> Normalize.
  * Bit-exact with Pillow's 8-bit bicubic resample; only the cropped rows / columns are produced.

@@ -828,6 +828,63 @@ class FeatureAdapterFn(torch.autograd.Function):
         return None, (g1.reshape(s1).to(d1) if need1 else None), (g2.reshape(s2).to(d2) if need2 else None), None
 
 
+KNN_MAX_K = 32      # csrc/knn_graph.hip: KG_MAX_K
+
+
+def knn_graph(queries, base=None, k=16, self_offset=None):
+    """(idx int32 [n, k], sim f32 [n, k]): per row of `queries` [n, e] the k rows of `base` [m, e] of largest cosine, ordered (sim descending, index
+    ascending), on the native kernel (csrc/knn_graph.hip); the [n, m] similarities never reach memory.  base=None: pool on pool (a row is not its
+    own neighbour).  self_offset: query i is base row self_offset + i and is excluded for it (default: 0 when base is None, else nothing excluded).
+    Embeddings are taken un-normalised; finite rows of non-zero norm are the caller's duty."""
+    if not torch.is_tensor(queries) or queries.dim() != 2 or not queries.is_floating_point():
+        raise native.GripError(f"knn_graph: queries must be a floating-point [n, e] tensor, got {getattr(queries, 'shape', type(queries))}")
+    q = queries.detach().contiguous().float()
+    if base is None:
+        b = q
+        off = 0 if self_offset is None else int(self_offset)
+    else:
+        if not torch.is_tensor(base) or base.dim() != 2 or not base.is_floating_point() or base.shape[1] != q.shape[1] or base.device != q.device:
+            raise native.GripError(f"knn_graph: base must be a floating-point [m, {q.shape[1]}] tensor on {q.device}, got "
+                                   f"{getattr(base, 'shape', type(base))}")
+        b = base.detach().contiguous().float()
+        off = -1 if self_offset is None else int(self_offset)
+    require_gpu(q.device)
+    (n, e), m, k = q.shape, b.shape[0], int(k)
+    lib = native.lib()
+    nbytes = c_size_t()
+    native.check(lib.grip_knn_graph_workspace(n, m, e, k, byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=q.device)
+    idx = torch.empty(n, k, dtype=torch.int32, device=q.device)
+    sim = torch.empty(n, k, dtype=torch.float32, device=q.device)
+    native.check(lib.grip_knn_graph(_ptr(q), _ptr(b), n, m, e, k, off, _ptr(idx), _ptr(sim), _ptr(ws), ws.numel(), _stream()))
+    return idx, sim
+
+
+def label_propagate(probs, idx, sim, alpha, gamma, iters):
+    """(Z f32 [n, c], pred int32 [n]): `iters` steps of Z <- (1 - alpha) probs + alpha W Z on the directed kNN graph (idx, sim) of engine.knn_graph,
+    W = softmax(gamma sim) over each row's neighbours; pred is the first arg-max of Z's rows (csrc/knn_graph.hip)."""
+    if not torch.is_tensor(probs) or probs.dim() != 2 or not probs.is_floating_point():
+        raise native.GripError(f"label_propagate: probs must be a floating-point [n, c] tensor, got {getattr(probs, 'shape', type(probs))}")
+    n, c = probs.shape
+    if not torch.is_tensor(idx) or not torch.is_tensor(sim) or idx.dim() != 2 or idx.shape[0] != n or tuple(sim.shape) != tuple(idx.shape) \
+            or idx.dtype != torch.int32 or sim.dtype != torch.float32 or idx.device != probs.device or sim.device != probs.device:
+        raise native.GripError(f"label_propagate: idx (int32) and sim (f32) must both be [{n}, k] on {probs.device}, got "
+                               f"{getattr(idx, 'shape', None)} {getattr(idx, 'dtype', None)} and {getattr(sim, 'shape', None)} {getattr(sim, 'dtype', None)}")
+    require_gpu(probs.device)
+    p = probs.detach().contiguous().float()
+    ix, sm = idx.contiguous(), sim.contiguous()
+    k = ix.shape[1]
+    lib = native.lib()
+    nbytes = c_size_t()
+    native.check(lib.grip_label_propagate_workspace(n, c, k, byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=p.device)
+    out = torch.empty_like(p)
+    pred = torch.empty(n, dtype=torch.int32, device=p.device)
+    native.check(lib.grip_label_propagate(_ptr(p), _ptr(ix), _ptr(sm), float(alpha), float(gamma), int(iters), n, c, k, _ptr(out), _ptr(pred), _ptr(ws),
+                                          ws.numel(), _stream()))
+    return out, pred
+
+
 def leaderboard_scan(probs, pred, path_rank, k):
     """Host scan (exact, sequential).  probs [n,c] f32 CPU, pred [n] int32 CPU, path_rank [n] int64 CPU."""
     import numpy as np

@@ -68,6 +68,14 @@ class TrainingStrategy:
         if bool(getattr(config, "CLIP_ADAPTER", False)) and self.modality != "text":
             log.info(f"CLIP_ADAPTER is ignored by the {self.modality} strategies: their image features move with the prompt (textual strategies only)")
         self.clip_adapter()      # (raises when CLIP_ADAPTER and TIP_ADAPTER are both set)
+        # LABEL_PROPAGATION (all modalities, default False): every pseudolabel pass propagates the head's probabilities over the pool's kNN graph
+        # (LP_K 16, LP_ALPHA 0.8, LP_GAMMA 10, LP_ITERS 10: untuned).  Textual strategies keep the graph per pool -- their image tower is frozen, the graph
+        # is an invariant of the run; visual and multimodal strategies rebuild it every pass: their features move with the prompt.
+        self.label_prop = None
+        if bool(getattr(config, "LABEL_PROPAGATION", False)):
+            self.label_prop = pl.LabelPropagation(k=int(getattr(config, "LP_K", 16)), alpha=float(getattr(config, "LP_ALPHA", 0.8)),
+                                                  gamma=float(getattr(config, "LP_GAMMA", 10.0)), iters=int(getattr(config, "LP_ITERS", 10)),
+                                                  keep_graphs=self.modality == "text")
         self.declare_custom_encoder()
         self.initialize_prompts_parameters()
 
@@ -256,7 +264,8 @@ class TrainingStrategy:
             return train_data
         c = self.config
         pseudo_classes = self.classes if self.paradigm in ("ssl", "ul") else self.unseen_classes
-        with pl.pool_cache(self.pool_cache):      # the frozen-CLIP pass runs the same towers over the same pool as the trained-prompt passes after it
+        # the frozen-CLIP pass runs the same towers over the same pool as the trained-prompt passes after it
+        with pl.pool_cache(self.pool_cache), pl.label_propagation(self.label_prop):
             pseudolabel_top_k(c, c.DATASET_NAME, int(c.N_PSEUDOSHOTS), self.template, unlabeled_data, pseudo_classes, self.transform,
                               self.clip_model, self.label_to_idx, self.device, c.VIS_ENCODER, getattr(c, "SPLIT_SEED", 0))
         return self.merge_pseudolabels(train_data, unlabeled_data)
@@ -679,8 +688,10 @@ class TrainingStrategy:
         images = _pool_images(unlabeled_data, self.transform, self.device)
         labels = [self.label_to_idx[c] for c in classes]
         paths = list(unlabeled_data.filepaths)      # the pool as passed to the pass (grip_train resets it to the original list every iteration): the cache's key
-        with pl.pool_cache(self.pool_cache):        # (None for the visual / multimodal strategies: nothing is installed)
-            if pl.mode() == "identical" and not self.clip_model.exact:
+        with pl.pool_cache(self.pool_cache), pl.label_propagation(self.label_prop):        # (None: nothing is installed)
+            if pl.propagation() is not None:
+                log.info(f"{pl.propagation()} is installed: the pass propagates over the pool and takes the plain branch (no reference list to be identical to)")
+            if pl.mode() == "identical" and pl.propagation() is None and not self.clip_model.exact:
                 # the lists the reference's fp32 pass would produce with these prompts: f16 screen + exact refinement
                 twin = self.clip_model.exact_twin()
                 txt, vprompt = self.trained_text_features(classes, twin)

@@ -93,6 +93,12 @@ _SIGS = {
     "grip_feature_adapter_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "grip_feature_adapter_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                               c_size_t, c_void_p]),
+    # (ABI 9 additions) label propagation over a pool: kNN graph of the embeddings + random walk of the probabilities (csrc/knn_graph.hip)
+    "grip_knn_graph_workspace": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "grip_knn_graph": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "grip_label_propagate_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "grip_label_propagate": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                     c_void_p]),
     "grip_preprocess_image": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                       c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "grip_preprocess_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

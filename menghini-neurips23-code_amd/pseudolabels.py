@@ -900,9 +900,99 @@ def identical_lists(visual16, visual32, images, txt_exact, scale, paths, class_l
     return [paths[i] for i in img], [class_labels[int(c)] for c in cls]
 
 
+# ------------------------------------------------------------------------------------------ transductive label propagation over the pool
+class LabelPropagation:
+    """Settings of the transductive pseudolabel pass (off unless installed by label_propagation()): the head's probabilities of the whole pool are
+    propagated over the pool's own kNN graph before the leaderboard scan -- images that lie together in the embedding space mostly share a class
+    (Zhu & Ghahramani 2002; Zhou et al. 2004; ZLaP, CVPR 2024).  k neighbours per image (cosine of the embeddings), edge weights
+    softmax(gamma * cosine) per row, `iters` steps of Z <- (1 - alpha) P + alpha W Z (engine.knn_graph / engine.label_propagate: a random walk on the
+    directed graph, not ZLaP's symmetrised solve).  The defaults are untuned.
+    keep_graphs: keep (idx, sim) per pool, keyed by the ordered paths like PoolFeatureCache -- for callers whose image tower is frozen and
+    prompt-free (the textual strategies: the graph is an invariant of the run); a caller whose features move builds it every pass (the default)."""
+
+    def __init__(self, k=16, alpha=0.8, gamma=10.0, iters=10, keep_graphs=False):
+        self.k, self.alpha, self.gamma, self.iters = int(k), float(alpha), float(gamma), int(iters)
+        if not 1 <= self.k <= engine.KNN_MAX_K:
+            raise ValueError(f"LabelPropagation: k = {k} (1 .. {engine.KNN_MAX_K})")
+        if not 0.0 <= self.alpha < 1.0:
+            raise ValueError(f"LabelPropagation: alpha = {alpha} (0 <= alpha < 1)")
+        if not 0.0 <= self.gamma < float("inf"):
+            raise ValueError(f"LabelPropagation: gamma = {gamma} (a finite gamma >= 0)")
+        if self.iters < 1:
+            raise ValueError(f"LabelPropagation: iters = {iters} (at least 1)")
+        self.keep_graphs = bool(keep_graphs)
+        self._graphs = []           # [(path tuple, fingerprint of the embeddings, idx, sim)], most recently used first
+        self.graphs_built = 0
+
+    def graph(self, img_emb, paths=None):
+        """(idx, sim) of the pool's kNN graph (min(k, N - 1) neighbours): built, or the kept one of this ordered pool.  The paths name the images,
+        not the features: a kept graph is handed out only while the embeddings' fingerprint (two float64 sums: one small reduction and one
+        host read per pass) is the one it was built from, so other features behind the same paths -- another tower, a prompt, an adapter -- rebuild
+        it instead of meeting a stale graph."""
+        n = img_emb.shape[0]
+        key = mark = None
+        if self.keep_graphs and paths is not None:
+            key = paths if isinstance(paths, tuple) else tuple(paths)
+            ramp = torch.arange(1, n + 1, dtype=torch.float64, device=img_emb.device)      # (position-weighted: a permutation of the rows moves it)
+            mark = (tuple(img_emb.shape), str(img_emb.device),
+                    *torch.stack([img_emb.sum(dtype=torch.float64), torch.dot(img_emb.sum(dim=1, dtype=torch.float64), ramp)]).tolist())
+            for i, (p, held, idx, sim) in enumerate(self._graphs):
+                if len(p) == len(key) and p == key:
+                    if held != mark:
+                        del self._graphs[i]         # the same pool with other features: the graph is rebuilt below
+                        break
+                    if i:
+                        self._graphs.insert(0, self._graphs.pop(i))
+                    return idx, sim
+        idx, sim = engine.knn_graph(img_emb, k=min(self.k, n - 1))
+        self.graphs_built += 1
+        if key is not None:
+            self._graphs.insert(0, (key, mark, idx, sim))
+            del self._graphs[4:]
+        return idx, sim
+
+    def clear(self):
+        self._graphs.clear()
+
+    def __repr__(self):
+        return f"LabelPropagation(k={self.k}, alpha={self.alpha}, gamma={self.gamma}, iters={self.iters})"
+
+
+_PROPAGATION = []   # settings installed by label_propagation(), innermost last.  Empty unless a caller opened one: every pass is per-image by default
+
+
+@contextlib.contextmanager
+def label_propagation(lp):
+    """Install `lp` (a LabelPropagation, or None: no-op) for the pseudolabel passes underneath -- how it reaches the reference-named
+    compute_pseudo_labels / pseudolabel_top_k, whose signatures are the reference's.  While one is installed pseudolabel_from_features propagates, the
+    callers that would pick identical_lists take their plain branch (no reference list can be identical to a propagated one) and pseudolabel_top_k
+    names its pickle `..._pseudolabels_lp_split_...`."""
+    if lp is None:
+        yield None
+        return
+    if not isinstance(lp, LabelPropagation):
+        raise TypeError(f"label_propagation: expected a LabelPropagation or None, got {type(lp).__name__}")
+    _PROPAGATION.append(lp)
+    try:
+        yield lp
+    finally:
+        _PROPAGATION.pop()
+
+
+def propagation():
+    """The innermost installed LabelPropagation, or None."""
+    return _PROPAGATION[-1] if _PROPAGATION else None
+
+
 @torch.no_grad()
 def pseudolabel_from_features(img_emb, txt_emb, scale, paths, class_labels, k, argmax_on="probs"):
-    """Head + scan.  argmax_on: "probs" (compute_pseudo_labels, :39) or "logits" (assign_pseudo_labels)."""
+    """Head + scan.  argmax_on: "probs" (compute_pseudo_labels, :39) or "logits" (assign_pseudo_labels).  With a LabelPropagation installed the
+    scan runs on the propagated probabilities Z of the whole (gathered, on every rank alike) pool and on arg-max Z, for both forms of argmax_on."""
     logits, probs, am_l, am_p = engine.cosine_head(img_emb, txt_emb, scale)
+    lp = propagation()
+    if lp is not None and img_emb.shape[0] >= 2:        # (a pool of one image has no neighbour to hear from)
+        idx, sim = lp.graph(img_emb, paths)
+        z, z_pred = engine.label_propagate(probs, idx, sim, lp.alpha, lp.gamma, lp.iters)
+        return leaderboard(z.cpu().numpy(), z_pred.cpu().numpy(), paths, class_labels, k)
     pred = (am_p if argmax_on == "probs" else am_l).cpu().numpy()
     return leaderboard(probs.cpu().numpy(), pred, paths, class_labels, k)

@@ -75,7 +75,9 @@ def compute_pseudo_labels(k, template, dataset, classnames, transform, clip_mode
     images = _pool_images(dataset, transform, device)
     scale = clip_model.logit_scale.exp().item()
     log.info(f"Compute {k} pseudo-labeles")
-    if pl.mode() == "identical" and not getattr(clip_model, "exact", False) and hasattr(clip_model, "exact_twin"):
+    if pl.propagation() is not None:
+        log.info(f"{pl.propagation()} is installed: the pass propagates over the pool and takes the plain branch (no reference list to be identical to)")
+    if pl.mode() == "identical" and pl.propagation() is None and not getattr(clip_model, "exact", False) and hasattr(clip_model, "exact_twin"):
         # the fp32 scan's lists at close to f16 throughput: f16 screen, exact re-encode of the undecidable rows only
         twin = clip_model.exact_twin()
         with torch.no_grad():
@@ -102,7 +104,8 @@ def compute_pseudo_labels(k, template, dataset, classnames, transform, clip_mode
 
 def pseudolabel_top_k(config, data_name, k, template, dataset, classnames, transform, clip_model, label_to_idx, device,
                       vis_encoder, split_seed):
-    filename = f"pseudolabels/{data_name}_{vis_encoder.replace('/', '')}_{config.LEARNING_PARADIGM}_{config.MODEL}_{k}_pseudolabels_split_{split_seed}.pickle"
+    lp = "lp_" if pl.propagation() is not None else ""      # a propagated list and a reference-style one never share a cache file
+    filename = f"pseudolabels/{data_name}_{vis_encoder.replace('/', '')}_{config.LEARNING_PARADIGM}_{config.MODEL}_{k}_pseudolabels_{lp}split_{split_seed}.pickle"
     if os.path.exists(filename):
         with open(filename, "rb") as f:
             pseudolabels = pickle.load(f)
