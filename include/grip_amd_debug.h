@@ -29,6 +29,15 @@ int grip_debug_gemm_train(int epi, const void* A, const void* W, int M, int N, i
                           float* stat_part, float* rowstat, const float* colsum, const float* stat_in, int stat_parts, int ksplit,
                           float* coop_scratch, int* coop_counter, int m_pad, void* stream);
 int grip_debug_coop_split(int M, int N, int K);
+/* One f16 GEMM launch with every field of its argument block given (tests/test_gpu_gemm_kernels.py): what the four hooks above fix --
+ * ldc = N, no compensated stream, rot_rows by hook -- is free here.  out / out2 / resid / aux are [M, ldc] (out may point N columns into a wider row);
+ * resid_lo [M, ldc] f16 is the low half of a compensated residual stream (epi 3 with stat_part: read, and rewritten in place); epi 6 multiplies by scalar;
+ * ksplit > 1 is split-K (epi 0: split_stride floats between the partials) or the cooperative form (epi 3 with coop_scratch and coop_counter).  Nothing
+ * is checked beyond what the launcher itself checks. */
+int grip_debug_gemm_args(int epi, const void* A, const void* W, int M, int N, int K, int ldc, const float* bias, const void* resid, void* resid_lo,
+                         const void* aux, void* out, void* out2, float scalar, float* stat_part, float* rowstat, const float* colsum,
+                         const float* stat_in, int stat_parts, int ksplit, int64_t split_stride, float* coop_scratch, int* coop_counter, int m_pad,
+                         int variant, int rot_rows, void* stream);
 /* Split-K product (the input-gradient GEMMs of the prompt steps): out = ksplit partial [M, N] f32 buffers, split_stride floats apart,
  * partial p = A[:, Kp] W[:, Kp]^T over the p-th K range.  ksplit = 0: the launcher's own choice; *ksplit_used receives the factor. */
 int grip_debug_gemm_splitk(const void* A, const void* W, int M, int N, int K, float* out, int ksplit, int64_t split_stride, int* ksplit_used,

@@ -818,6 +818,19 @@ extern "C" int grip_debug_gemm_train(int epi, const void* A, const void* W, int 
     a.ksplit = ksplit; a.coop_scratch = coop_scratch; a.coop_counter = coop_counter;
     return launch_gemm(epi, a, (hipStream_t)stream);
 }
+// Every field of GemmArgs that an f16 launch reads, as given (tests/test_gpu_gemm_kernels.py): ldc != N, the compensated stream (resid_lo), EPI_F32_SCALE,
+// split-K and the cooperative form on any variant.  No logic of its own: what launch_gemm refuses is refused.
+extern "C" int grip_debug_gemm_args(int epi, const void* A, const void* W, int M, int N, int K, int ldc, const float* bias, const void* resid, void* resid_lo,
+                                    const void* aux, void* out, void* out2, float scalar, float* stat_part, float* rowstat, const float* colsum,
+                                    const float* stat_in, int stat_parts, int ksplit, int64_t split_stride, float* coop_scratch, int* coop_counter, int m_pad,
+                                    int variant, int rot_rows, void* stream) {
+    GemmArgs a{};
+    a.A = A; a.W = W; a.M = M; a.N = N; a.K = K; a.ldc = ldc; a.m_pad = m_pad; a.variant = variant; a.rot_rows = rot_rows;
+    a.bias = bias; a.resid = resid; a.resid_lo = (half_t*)resid_lo; a.aux = aux; a.out = out; a.out2 = out2; a.scalar = scalar;
+    a.stat_part = stat_part; a.rowstat = rowstat; a.colsum = colsum; a.stat_in = stat_in; a.stat_parts = stat_parts;
+    a.ksplit = ksplit; a.split_stride = split_stride; a.coop_scratch = coop_scratch; a.coop_counter = coop_counter;
+    return launch_gemm(epi, a, (hipStream_t)stream);
+}
 extern "C" int grip_debug_coop_split(int M, int N, int K) { return gemm_pick_coop_split(M, N, K); }
 extern "C" int grip_debug_ln_fold(const void* W, const float* gamma, const float* beta, const float* bias, void* Wg, float* colsum, float* bias_out,
                                   int N, int K, const float* stat_part, int parts, float* rowstat, int M, int d, void* stream) {

@@ -127,6 +127,8 @@ _DEBUG_SIGS = {          # kernel-level test hooks (csrc/tower.hip), not part of
                                    c_int, c_int, c_void_p]),
     "grip_debug_gemm_train": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "grip_debug_gemm_args": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "grip_debug_coop_split": (c_int, [c_int, c_int, c_int]),
     "grip_debug_gemm_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int, ctypes.c_char_p, c_int]),
     "grip_debug_gemm_splitk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_void_p]),
