@@ -378,6 +378,40 @@ int grip_label_propagate(const float* probs, const int32_t* idx, const float* si
                          float* out, int32_t* argmax_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 9 additions) Transductive GMM pseudolabelling over a pool (pseudolabels.TransductiveGMM; csrc/gmm_transduce.hip), after TransCLIP-ZS
+ * (Zanella, Gerin, Ben Ayed, NeurIPS 2024): one Gaussian per class with a shared diagonal covariance on the pool's image embeddings, the assignments
+ * anchored to the text head's probabilities and smoothed over the directed kNN graph of grip_knn_graph.  The recursion is the one written here, NOT
+ * that paper's code: the first centres come from an M-step on the head's probabilities (no top-8 confident samples), the graph is directed, there is
+ * no few-shot term.  A caller starts from Z = probs and alternates the two calls.  All tensors f32 / int32 on the device; no atomics.
+ *
+ * grip_gmm_mstep: z [n, c] (non-negative weights), feats [n, e] (unit rows are the CALLER's duty: the kernels take them as given)
+ *   count_out[c]   = sum_i z_ic
+ *   mean_out[c, :] = (sum_i z_ic feats_i) / count_out[c]; the zero vector where count_out[c] is exactly 0
+ *   var_out[d]     = max(var_floor, (1 / n) sum_i sum_c z_ic (feats_id - mean_out[c, d])^2)        (the direct two-pass form)
+ *   The rows are reduced over a FIXED partition (chunks of 256 rows for the sums, of 32 for the variance) and the partials added in an order that n
+ *   alone fixes (contiguous slices of the chunks, each in ascending order, then the slices in ascending order): the result is bit-identical from call
+ *   to call and does not depend on how many workgroups ran at once.  The sums run on the f32 MFMA.
+ *   e a multiple of 4 up to 2048, any c >= 1, n >= 1, var_floor > 0; feats and mean_out 16-byte aligned; no output may alias z or feats.
+ *
+ * grip_gmm_estep: feats [n, e], mean [c, e], var [e], probs [n, c], (idx, sim) [n, k] the directed graph (idx values in [0, n) are the caller's duty),
+ *   z_in [n, c] the current assignments:
+ *   G_ic = feats_i . (mean_c / var) - 1/2 sum_d mean_cd^2 / var_d      (the class-independent terms of the log-density cancel in the softmax)
+ *   then z_iters Jacobi sweeps   A_ic = G_ic + lam log(max(probs_ic, 2^-126)) + sum_j max(0, sim_ij) Z_{idx_ij, c},   Z_i <- softmax_c(A_i)
+ *   (the maximum is subtracted first, the neighbours are added in list order, every sweep reads the previous sweep's Z: ping-pong between z_out and
+ *   the workspace, never in place).  z_out [n, c]: the last sweep's Z; argmax_out [n] int32 or NULL: the first index of the maximum of z_out's row.
+ *   G is computed once per call on the f32 MFMA (each score one chain over e in ascending order: bit-equal classes score bit-equally) and kept in
+ *   the workspace.  lam >= 0, z_iters >= 1, 1 <= k <= 32, e a multiple of 4 up to 2048, any c >= 1, n >= 1; feats, mean and var 16-byte aligned;
+ *   z_out must not alias z_in or probs.
+ * Both calls refuse out-of-range arguments with nothing written; the workspace calls need no device. */
+int grip_gmm_mstep_workspace(int n, int c, int e, size_t* bytes);
+int grip_gmm_mstep(const float* z, const float* feats, int n, int c, int e, float var_floor, float* count_out, float* mean_out, float* var_out,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int grip_gmm_estep_workspace(int n, int c, int e, int k, size_t* bytes);
+int grip_gmm_estep(const float* feats, const float* mean, const float* var, const float* probs, const int32_t* idx, const float* sim, const float* z_in,
+                   float lam, int z_iters, int n, int c, int e, int k, float* z_out, int32_t* argmax_out, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CLIP preprocessing of one decoded image: the `_transform` the reference applies per item on the host
  * (data/dataset.py:64-79 via clip.load's preprocess): Resize(n_px, BICUBIC) -> CenterCrop(n_px) -> ToTensor -> Normalize.
  * Bit-exact with Pillow's 8-bit bicubic resample; only the cropped rows / columns are produced.

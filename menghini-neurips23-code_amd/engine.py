@@ -885,6 +885,84 @@ def label_propagate(probs, idx, sim, alpha, gamma, iters):
     return out, pred
 
 
+GMM_MSTEP_ROWS = 256    # csrc/gmm_transduce.hip: GM_ROWS, the fixed row partition of the M-step's sums
+
+
+def _gmm_operand(who, name, t, shape, like=None, dtype=torch.float32):
+    if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or (like is not None and t.device != like.device):
+        raise native.GripError(f"{who}: {name} must be a {str(dtype).replace('torch.', '')} {list(shape)} tensor" +
+                               (f" on {like.device}" if like is not None else "") +
+                               f", got {getattr(t, 'shape', type(t))} {getattr(t, 'dtype', None)}")
+    return t.detach().contiguous()
+
+
+def gmm_mstep(z, feats, var_floor=1e-8):
+    """(count f32 [c], mean f32 [c, e], var f32 [e]) of the weighted class Gaussians with a shared diagonal covariance: count_c = sum_i z_ic,
+    mean_c = sum_i z_ic feats_i / count_c (zero where the count is 0), var_d = max(var_floor, mean_i sum_c z_ic (feats_id - mean_cd)^2), on the
+    native kernels (csrc/gmm_transduce.hip): no atomics, a fixed row partition, bit-identical from call to call.  feats is taken as given."""
+    if not torch.is_tensor(z) or z.dim() != 2 or not torch.is_tensor(feats) or feats.dim() != 2 or feats.shape[0] != z.shape[0]:
+        raise native.GripError(f"gmm_mstep: z [n, c] and feats [n, e] expected, got {getattr(z, 'shape', type(z))} and {getattr(feats, 'shape', type(feats))}")
+    (n, c), e = z.shape, feats.shape[1]
+    zz = _gmm_operand("gmm_mstep", "z", z, (n, c))
+    f = _gmm_operand("gmm_mstep", "feats", feats, (n, e), zz)
+    require_gpu(zz.device)
+    lib = native.lib()
+    nbytes = c_size_t()
+    native.check(lib.grip_gmm_mstep_workspace(n, c, e, byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=zz.device)
+    count = torch.empty(c, dtype=torch.float32, device=zz.device)
+    mean = torch.empty(c, e, dtype=torch.float32, device=zz.device)
+    var = torch.empty(e, dtype=torch.float32, device=zz.device)
+    native.check(lib.grip_gmm_mstep(_ptr(zz), _ptr(f), n, c, e, float(var_floor), _ptr(count), _ptr(mean), _ptr(var), _ptr(ws), ws.numel(), _stream()))
+    return count, mean, var
+
+
+def gmm_estep(feats, mean, var, probs, idx, sim, z, lam=1.0, z_iters=5):
+    """(Z f32 [n, c], pred int32 [n]): the scores G_ic = feats_i . (mean_c / var) - 1/2 sum_d mean_cd^2 / var_d once on the f32 MFMA, then `z_iters`
+    Jacobi sweeps Z_i <- softmax_c(G_ic + lam log max(probs_ic, 2^-126) + sum_j max(0, sim_ij) Z_{idx_ij, c}) from Z = z over the directed graph
+    (idx, sim) of engine.knn_graph; pred is the first arg-max of Z's rows (csrc/gmm_transduce.hip).  feats is taken as given."""
+    if not torch.is_tensor(feats) or feats.dim() != 2 or not torch.is_tensor(probs) or probs.dim() != 2 or probs.shape[0] != feats.shape[0] \
+            or not torch.is_tensor(idx) or idx.dim() != 2:
+        raise native.GripError(f"gmm_estep: feats [n, e], probs [n, c] and idx [n, k] expected, got {getattr(feats, 'shape', type(feats))}, "
+                               f"{getattr(probs, 'shape', type(probs))} and {getattr(idx, 'shape', type(idx))}")
+    (n, e), c, k = feats.shape, probs.shape[1], idx.shape[1]
+    f = _gmm_operand("gmm_estep", "feats", feats, (n, e))
+    mu = _gmm_operand("gmm_estep", "mean", mean, (c, e), f)
+    v = _gmm_operand("gmm_estep", "var", var, (e,), f)
+    p = _gmm_operand("gmm_estep", "probs", probs, (n, c), f)
+    ix = _gmm_operand("gmm_estep", "idx", idx, (n, k), f, torch.int32)
+    sm = _gmm_operand("gmm_estep", "sim", sim, (n, k), f)
+    zz = _gmm_operand("gmm_estep", "z", z, (n, c), f)
+    require_gpu(f.device)
+    lib = native.lib()
+    nbytes = c_size_t()
+    native.check(lib.grip_gmm_estep_workspace(n, c, e, k, byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=f.device)
+    out = torch.empty(n, c, dtype=torch.float32, device=f.device)
+    pred = torch.empty(n, dtype=torch.int32, device=f.device)
+    native.check(lib.grip_gmm_estep(_ptr(f), _ptr(mu), _ptr(v), _ptr(p), _ptr(ix), _ptr(sm), _ptr(zz), float(lam), int(z_iters), n, c, e, k, _ptr(out),
+                                    _ptr(pred), _ptr(ws), ws.numel(), _stream()))
+    return out, pred
+
+
+def gmm_transduce(feats, probs, idx, sim, lam=1.0, iters=10, z_iters=5, var_floor=1e-8):
+    """(Z [n, c], pred int32 [n], mean [c, e], var [e], count [c]): the transductive GMM recursion of include/grip_amd.h (after TransCLIP-ZS, not that
+    code) from Z = probs: `iters` times an M-step on (Z, feats) and an E-step of `z_iters` sweeps.  feats are normalised to unit rows here (torch);
+    mean / var / count are the last M-step's, which can score images that were not in the pool."""
+    if int(iters) < 1:
+        raise native.GripError(f"gmm_transduce: iters = {iters} (at least 1)")
+    if not torch.is_tensor(feats) or feats.dim() != 2 or not feats.is_floating_point() or not torch.is_tensor(probs) or not probs.is_floating_point():
+        raise native.GripError(f"gmm_transduce: floating-point feats [n, e] and probs [n, c] expected, got {getattr(feats, 'shape', type(feats))} and "
+                               f"{getattr(probs, 'shape', type(probs))}")
+    f = torch.nn.functional.normalize(feats.detach().float(), dim=1).contiguous()
+    p = probs.detach().float().contiguous()
+    z, pred = p, None
+    for _ in range(int(iters)):
+        count, mean, var = gmm_mstep(z, f, var_floor)
+        z, pred = gmm_estep(f, mean, var, p, idx, sim, z, lam, z_iters)
+    return z, pred, mean, var, count
+
+
 def leaderboard_scan(probs, pred, path_rank, k):
     """Host scan (exact, sequential).  probs [n,c] f32 CPU, pred [n] int32 CPU, path_rank [n] int64 CPU."""
     import numpy as np

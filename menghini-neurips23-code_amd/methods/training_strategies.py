@@ -76,8 +76,28 @@ class TrainingStrategy:
             self.label_prop = pl.LabelPropagation(k=int(getattr(config, "LP_K", 16)), alpha=float(getattr(config, "LP_ALPHA", 0.8)),
                                                   gamma=float(getattr(config, "LP_GAMMA", 10.0)), iters=int(getattr(config, "LP_ITERS", 10)),
                                                   keep_graphs=self.modality == "text")
+        # TRANSDUCTIVE_GMM (all modalities, default False): every pseudolabel pass fits one Gaussian per class to the pool's embeddings and scans the
+        # graph-regularised assignments (pl.TransductiveGMM, after TransCLIP-ZS; GMM_K 3, GMM_LAMBDA 1.0, GMM_ITERS 10, GMM_Z_ITERS 5: untuned).  The graph is
+        # kept or rebuilt as for LABEL_PROPAGATION.  `predict`, validation, the Tip cache and the adapter do not see it.
+        self.gmm = None
+        if bool(getattr(config, "TRANSDUCTIVE_GMM", False)):
+            if self.label_prop is not None:
+                raise ValueError("TRANSDUCTIVE_GMM and LABEL_PROPAGATION are two different transductions of the same pool: set one of them")
+            self.gmm = pl.TransductiveGMM(k=int(getattr(config, "GMM_K", 3)), lam=float(getattr(config, "GMM_LAMBDA", 1.0)),
+                                          iters=int(getattr(config, "GMM_ITERS", 10)), z_iters=int(getattr(config, "GMM_Z_ITERS", 5)),
+                                          keep_graphs=self.modality == "text")
         self.declare_custom_encoder()
         self.initialize_prompts_parameters()
+
+    def transduction(self):
+        """What the pseudolabel passes install with pl.label_propagation(): the LabelPropagation, the TransductiveGMM, or None."""
+        return self.label_prop if self.label_prop is not None else self.gmm
+
+    @property
+    def gmm_state(self):
+        """(mean [c, e], var [e]) of the most recent TRANSDUCTIVE_GMM pass (None before the first, or with the switch off): the class Gaussians of
+        the pool, which can score images that were not in it."""
+        return None if self.gmm is None else self.gmm.state
 
     # ------------------------------------------------------------------ encoders / prompts / model
     def declare_custom_encoder(self):
@@ -265,7 +285,7 @@ class TrainingStrategy:
         c = self.config
         pseudo_classes = self.classes if self.paradigm in ("ssl", "ul") else self.unseen_classes
         # the frozen-CLIP pass runs the same towers over the same pool as the trained-prompt passes after it
-        with pl.pool_cache(self.pool_cache), pl.label_propagation(self.label_prop):
+        with pl.pool_cache(self.pool_cache), pl.label_propagation(self.transduction()):
             pseudolabel_top_k(c, c.DATASET_NAME, int(c.N_PSEUDOSHOTS), self.template, unlabeled_data, pseudo_classes, self.transform,
                               self.clip_model, self.label_to_idx, self.device, c.VIS_ENCODER, getattr(c, "SPLIT_SEED", 0))
         return self.merge_pseudolabels(train_data, unlabeled_data)
@@ -688,7 +708,7 @@ class TrainingStrategy:
         images = _pool_images(unlabeled_data, self.transform, self.device)
         labels = [self.label_to_idx[c] for c in classes]
         paths = list(unlabeled_data.filepaths)      # the pool as passed to the pass (grip_train resets it to the original list every iteration): the cache's key
-        with pl.pool_cache(self.pool_cache), pl.label_propagation(self.label_prop):        # (None: nothing is installed)
+        with pl.pool_cache(self.pool_cache), pl.label_propagation(self.transduction()):        # (None: nothing is installed)
             if pl.propagation() is not None:
                 log.info(f"{pl.propagation()} is installed: the pass propagates over the pool and takes the plain branch (no reference list to be identical to)")
             if pl.mode() == "identical" and pl.propagation() is None and not self.clip_model.exact:

@@ -99,6 +99,13 @@ _SIGS = {
     "grip_label_propagate_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
     "grip_label_propagate": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                      c_void_p]),
+    # (ABI 9 additions) transductive GMM pseudolabelling over a pool: class Gaussians fitted to the embeddings + graph-regularised assignments
+    # (csrc/gmm_transduce.hip)
+    "grip_gmm_mstep_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "grip_gmm_mstep": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "grip_gmm_estep_workspace": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "grip_gmm_estep": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                               c_void_p, c_void_p, c_size_t, c_void_p]),
     "grip_preprocess_image": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                       c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "grip_preprocess_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

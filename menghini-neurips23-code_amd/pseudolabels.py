@@ -901,25 +901,15 @@ def identical_lists(visual16, visual32, images, txt_exact, scale, paths, class_l
 
 
 # ------------------------------------------------------------------------------------------ transductive label propagation over the pool
-class LabelPropagation:
-    """Settings of the transductive pseudolabel pass (off unless installed by label_propagation()): the head's probabilities of the whole pool are
-    propagated over the pool's own kNN graph before the leaderboard scan -- images that lie together in the embedding space mostly share a class
-    (Zhu & Ghahramani 2002; Zhou et al. 2004; ZLaP, CVPR 2024).  k neighbours per image (cosine of the embeddings), edge weights
-    softmax(gamma * cosine) per row, `iters` steps of Z <- (1 - alpha) P + alpha W Z (engine.knn_graph / engine.label_propagate: a random walk on the
-    directed graph, not ZLaP's symmetrised solve).  The defaults are untuned.
+class _PoolGraph:
+    """The kNN graph of a pool for the transductive passes (LabelPropagation, TransductiveGMM): built per pass, or kept per pool.
     keep_graphs: keep (idx, sim) per pool, keyed by the ordered paths like PoolFeatureCache -- for callers whose image tower is frozen and
     prompt-free (the textual strategies: the graph is an invariant of the run); a caller whose features move builds it every pass (the default)."""
 
-    def __init__(self, k=16, alpha=0.8, gamma=10.0, iters=10, keep_graphs=False):
-        self.k, self.alpha, self.gamma, self.iters = int(k), float(alpha), float(gamma), int(iters)
+    def __init__(self, k, keep_graphs=False):
+        self.k = int(k)
         if not 1 <= self.k <= engine.KNN_MAX_K:
-            raise ValueError(f"LabelPropagation: k = {k} (1 .. {engine.KNN_MAX_K})")
-        if not 0.0 <= self.alpha < 1.0:
-            raise ValueError(f"LabelPropagation: alpha = {alpha} (0 <= alpha < 1)")
-        if not 0.0 <= self.gamma < float("inf"):
-            raise ValueError(f"LabelPropagation: gamma = {gamma} (a finite gamma >= 0)")
-        if self.iters < 1:
-            raise ValueError(f"LabelPropagation: iters = {iters} (at least 1)")
+            raise ValueError(f"{type(self).__name__}: k = {k} (1 .. {engine.KNN_MAX_K})")
         self.keep_graphs = bool(keep_graphs)
         self._graphs = []           # [(path tuple, fingerprint of the embeddings, idx, sim)], most recently used first
         self.graphs_built = 0
@@ -954,8 +944,65 @@ class LabelPropagation:
     def clear(self):
         self._graphs.clear()
 
+
+class LabelPropagation(_PoolGraph):
+    """Settings of the transductive pseudolabel pass (off unless installed by label_propagation()): the head's probabilities of the whole pool are
+    propagated over the pool's own kNN graph before the leaderboard scan -- images that lie together in the embedding space mostly share a class
+    (Zhu & Ghahramani 2002; Zhou et al. 2004; ZLaP, CVPR 2024).  k neighbours per image (cosine of the embeddings), edge weights
+    softmax(gamma * cosine) per row, `iters` steps of Z <- (1 - alpha) P + alpha W Z (engine.knn_graph / engine.label_propagate: a random walk on the
+    directed graph, not ZLaP's symmetrised solve).  The defaults are untuned.  keep_graphs: see _PoolGraph."""
+    infix = "lp_"       # of the pseudolabel pickle's name (utils.clip_pseudolabels.pseudolabel_top_k)
+
+    def __init__(self, k=16, alpha=0.8, gamma=10.0, iters=10, keep_graphs=False):
+        super().__init__(k, keep_graphs)
+        self.alpha, self.gamma, self.iters = float(alpha), float(gamma), int(iters)
+        if not 0.0 <= self.alpha < 1.0:
+            raise ValueError(f"LabelPropagation: alpha = {alpha} (0 <= alpha < 1)")
+        if not 0.0 <= self.gamma < float("inf"):
+            raise ValueError(f"LabelPropagation: gamma = {gamma} (a finite gamma >= 0)")
+        if self.iters < 1:
+            raise ValueError(f"LabelPropagation: iters = {iters} (at least 1)")
+
+    def transduce(self, img_emb, probs, paths=None):
+        """(Z, pred) of the pool: the propagated probabilities and their first arg-max."""
+        idx, sim = self.graph(img_emb, paths)
+        return engine.label_propagate(probs, idx, sim, self.alpha, self.gamma, self.iters)
+
     def __repr__(self):
         return f"LabelPropagation(k={self.k}, alpha={self.alpha}, gamma={self.gamma}, iters={self.iters})"
+
+
+class TransductiveGMM(_PoolGraph):
+    """Settings of the transductive GMM pseudolabel pass (off unless installed by label_propagation()), after TransCLIP-ZS (Zanella, Gerin, Ben Ayed,
+    NeurIPS 2024): one Gaussian per class with a shared diagonal covariance is fitted to the pool's unit image embeddings, the assignments Z are
+    anchored to the head's probabilities P by a KL term of weight `lam` and smoothed over the pool's directed kNN graph (k neighbours, affinity
+    max(0, cosine)); `iters` rounds of an M-step and an E-step of `z_iters` sweeps from Z = P (engine.gmm_transduce).  NOT TransCLIP's code: the first
+    centres come from an M-step on P instead of the top-8 confident samples, the graph is directed, there is no few-shot term.  The defaults are
+    untuned.  After a pass `state` holds the last (mean, var): they can score images that were not in the pool.  keep_graphs: see _PoolGraph."""
+    infix = "gmm_"      # of the pseudolabel pickle's name
+
+    def __init__(self, k=3, lam=1.0, iters=10, z_iters=5, var_floor=1e-8, keep_graphs=False):
+        super().__init__(k, keep_graphs)
+        self.lam, self.iters, self.z_iters, self.var_floor = float(lam), int(iters), int(z_iters), float(var_floor)
+        if not 0.0 <= self.lam < float("inf"):
+            raise ValueError(f"TransductiveGMM: lam = {lam} (a finite lam >= 0)")
+        if self.iters < 1:
+            raise ValueError(f"TransductiveGMM: iters = {iters} (at least 1)")
+        if self.z_iters < 1:
+            raise ValueError(f"TransductiveGMM: z_iters = {z_iters} (at least 1)")
+        if not 0.0 < self.var_floor < float("inf"):
+            raise ValueError(f"TransductiveGMM: var_floor = {var_floor} (a finite var_floor > 0)")
+        self.state = None           # (mean [c, e], var [e]) of the most recent pass
+
+    def transduce(self, img_emb, probs, paths=None):
+        """(Z, pred) of the pool: the assignments of the recursion and their first arg-max; keeps (mean, var) in `state`."""
+        idx, sim = self.graph(img_emb, paths)
+        z, pred, mean, var, _ = engine.gmm_transduce(img_emb, probs, idx, sim, self.lam, self.iters, self.z_iters, self.var_floor)
+        self.state = (mean, var)
+        return z, pred
+
+    def __repr__(self):
+        return f"TransductiveGMM(k={self.k}, lam={self.lam}, iters={self.iters}, z_iters={self.z_iters}, var_floor={self.var_floor})"
 
 
 _PROPAGATION = []   # settings installed by label_propagation(), innermost last.  Empty unless a caller opened one: every pass is per-image by default
@@ -963,15 +1010,15 @@ _PROPAGATION = []   # settings installed by label_propagation(), innermost last.
 
 @contextlib.contextmanager
 def label_propagation(lp):
-    """Install `lp` (a LabelPropagation, or None: no-op) for the pseudolabel passes underneath -- how it reaches the reference-named
-    compute_pseudo_labels / pseudolabel_top_k, whose signatures are the reference's.  While one is installed pseudolabel_from_features propagates, the
-    callers that would pick identical_lists take their plain branch (no reference list can be identical to a propagated one) and pseudolabel_top_k
-    names its pickle `..._pseudolabels_lp_split_...`."""
+    """Install `lp` (a LabelPropagation or a TransductiveGMM, or None: no-op) for the pseudolabel passes underneath -- how it reaches the
+    reference-named compute_pseudo_labels / pseudolabel_top_k, whose signatures are the reference's.  While one is installed pseudolabel_from_features
+    transduces with it, the callers that would pick identical_lists take their plain branch (no reference list can be identical to a transduced one) and
+    pseudolabel_top_k names its pickle after the object's `infix`: `..._pseudolabels_lp_split_...` / `..._pseudolabels_gmm_split_...`."""
     if lp is None:
         yield None
         return
-    if not isinstance(lp, LabelPropagation):
-        raise TypeError(f"label_propagation: expected a LabelPropagation or None, got {type(lp).__name__}")
+    if not isinstance(lp, (LabelPropagation, TransductiveGMM)):
+        raise TypeError(f"label_propagation: expected a LabelPropagation, a TransductiveGMM or None, got {type(lp).__name__}")
     _PROPAGATION.append(lp)
     try:
         yield lp
@@ -980,19 +1027,18 @@ def label_propagation(lp):
 
 
 def propagation():
-    """The innermost installed LabelPropagation, or None."""
+    """The innermost installed LabelPropagation / TransductiveGMM, or None."""
     return _PROPAGATION[-1] if _PROPAGATION else None
 
 
 @torch.no_grad()
 def pseudolabel_from_features(img_emb, txt_emb, scale, paths, class_labels, k, argmax_on="probs"):
-    """Head + scan.  argmax_on: "probs" (compute_pseudo_labels, :39) or "logits" (assign_pseudo_labels).  With a LabelPropagation installed the
-    scan runs on the propagated probabilities Z of the whole (gathered, on every rank alike) pool and on arg-max Z, for both forms of argmax_on."""
+    """Head + scan.  argmax_on: "probs" (compute_pseudo_labels, :39) or "logits" (assign_pseudo_labels).  With a LabelPropagation or a
+    TransductiveGMM installed the scan runs on its Z over the whole (gathered, on every rank alike) pool and on arg-max Z, for both forms of argmax_on."""
     logits, probs, am_l, am_p = engine.cosine_head(img_emb, txt_emb, scale)
     lp = propagation()
     if lp is not None and img_emb.shape[0] >= 2:        # (a pool of one image has no neighbour to hear from)
-        idx, sim = lp.graph(img_emb, paths)
-        z, z_pred = engine.label_propagate(probs, idx, sim, lp.alpha, lp.gamma, lp.iters)
+        z, z_pred = lp.transduce(img_emb, probs, paths)
         return leaderboard(z.cpu().numpy(), z_pred.cpu().numpy(), paths, class_labels, k)
     pred = (am_p if argmax_on == "probs" else am_l).cpu().numpy()
     return leaderboard(probs.cpu().numpy(), pred, paths, class_labels, k)
