@@ -412,6 +412,28 @@ int grip_gmm_estep(const float* feats, const float* mean, const float* var, cons
                    void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 9 additions) Balanced pseudolabel assignment over a pool (pseudolabels.BalancedAssignment; csrc/sinkhorn.hip): the [n, c] probabilities are
+ * treated as an optimal-transport problem -- rows sum to one, columns to n x a class prior -- and Sinkhorn-Knopp iterated on it (Cuturi 2013; SeLa,
+ * Asano et al. 2020; SwAV, Caron et al. 2020).  The row scaling is the softmax normaliser, so the only state between iterations is b [c]:
+ *   L_ic = tau log max(probs_ic, 2^-126)
+ *   b = log_scale_in (NULL: zeros);  `iters` times:   q_i = softmax_c(L_i + b),   s_c = sum_i q_ic,   b_c += log_target_c + log n - log max(s_c, 2^-126)
+ *   q_out_i = softmax_c(L_i + b),  pred_i = the first index of the maximum of q_out's row,  mass_c = sum_i q_out_ic,  log_scale_out = b
+ * (the row's maximum is subtracted first; L + b is one fused multiply-add).  Rows of q_out sum to one by construction; mass shows how far the columns
+ * still are from n exp(log_target).  There is NO epsilon-scaled cost and NO stopping rule: `iters` is how hard the balance is pressed, and iters = 0 is
+ * one bare softmax step under the given log_scale_in.  A column of probs that is zero in every row is legal: its b_c rises until the class has its share,
+ * filled with arbitrary rows.
+ *   probs, q_out [n, c]; log_target, log_scale_in, mass, log_scale_out [c] (log_target: the log of a prior that sums to one is the CALLER's duty);
+ *   pred [n] int32 or NULL.  tau > 0 and finite, iters >= 0, any n >= 1, any c >= 1.  q_out must not alias probs; log_scale_in may be log_scale_out.
+ *   The column sums run over a FIXED partition of the rows (chunks of 16, the rows of a chunk in ascending order) and the chunk partials are added in
+ *   an order that n alone fixes (64 contiguous slices of the chunks, each ascending, then the slices ascending): no atomics, bit-identical from call to
+ *   call.  With iters = 0 the bits of a row of q_out depend on that row and log_scale_in only -- not on n, not on the row's place.
+ *   One call enqueues 2 (iters + 1) launches; the workspace (grip_sinkhorn_workspace bytes) holds the chunk partials.  The workspace call needs no
+ *   device.  Out-of-range arguments are refused with nothing written. */
+int grip_sinkhorn_workspace(int n, int c, size_t* bytes);
+int grip_sinkhorn_balance(const float* probs, const float* log_target, const float* log_scale_in, float tau, int iters, int n, int c, float* q_out,
+                          int32_t* pred, float* mass, float* log_scale_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CLIP preprocessing of one decoded image: the `_transform` the reference applies per item on the host
  * (data/dataset.py:64-79 via clip.load's preprocess): Resize(n_px, BICUBIC) -> CenterCrop(n_px) -> ToTensor -> Normalize.
  * Bit-exact with Pillow's 8-bit bicubic resample; only the cropped rows / columns are produced.

@@ -4,6 +4,7 @@ torch is used for device memory, streams and autograd bookkeeping only; every FL
 encoders, the head and the losses runs in libgrip_amd.so (csrc/*.hip).
 """
 import ctypes
+import math
 import os
 import weakref
 from ctypes import byref, c_int64, c_size_t, c_uint64, c_void_p
@@ -961,6 +962,43 @@ def gmm_transduce(feats, probs, idx, sim, lam=1.0, iters=10, z_iters=5, var_floo
         count, mean, var = gmm_mstep(z, f, var_floor)
         z, pred = gmm_estep(f, mean, var, p, idx, sim, z, lam, z_iters)
     return z, pred, mean, var, count
+
+
+SINKHORN_ROWS = 16      # csrc/sinkhorn.hip: SK_ROWS, the fixed row partition of the column sums
+
+
+def sinkhorn_balance(probs, tau=1.0, iters=3, prior=None, log_scale=None):
+    """(Q f32 [n, c], pred int32 [n], mass f32 [c], log_scale f32 [c]): the balanced assignment of include/grip_amd.h on the native kernels
+    (csrc/sinkhorn.hip) -- `iters` Sinkhorn-Knopp iterations on probs ** tau from the column scaling exp(log_scale) (None: ones), then
+    Q_i = softmax_c(tau log probs_i + log_scale), its first arg-max and the column sums mass.  prior: None (uniform) or [c] finite positive weights,
+    normalised in float64 on the host; the columns are pressed towards n * prior.  iters = 0 is one bare step under the given log_scale.  The returned
+    log_scale continues the recursion in a later call.  No atomics, a fixed row partition, bit-identical from call to call."""
+    if not torch.is_tensor(probs) or probs.dim() != 2 or not probs.is_floating_point():
+        raise native.GripError(f"sinkhorn_balance: probs must be a floating-point [n, c] tensor, got {getattr(probs, 'shape', type(probs))}")
+    n, c = probs.shape
+    require_gpu(probs.device)
+    p = probs.detach().contiguous().float()
+    if prior is None:
+        log_target = torch.full((c,), math.log(1.0 / max(c, 1)), dtype=torch.float32, device=p.device)      # (filled on the device: no host copy per pass)
+    else:
+        if not torch.is_tensor(prior) or tuple(prior.shape) != (c,) or prior.is_complex():
+            raise native.GripError(f"sinkhorn_balance: prior must be a real [{c}] tensor, got {getattr(prior, 'shape', type(prior))}")
+        target = prior.detach().to("cpu", torch.float64)
+        if not bool((torch.isfinite(target) & (target > 0)).all()):
+            raise native.GripError("sinkhorn_balance: prior must hold finite positive weights")
+        log_target = torch.log(target / target.sum()).to(torch.float32).to(p.device)
+    b_in = None if log_scale is None else _gmm_operand("sinkhorn_balance", "log_scale", log_scale, (c,), p)
+    lib = native.lib()
+    nbytes = c_size_t()
+    native.check(lib.grip_sinkhorn_workspace(n, c, byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=p.device)
+    q = torch.empty_like(p)
+    pred = torch.empty(n, dtype=torch.int32, device=p.device)
+    mass = torch.empty(c, dtype=torch.float32, device=p.device)
+    b_out = torch.empty(c, dtype=torch.float32, device=p.device)
+    native.check(lib.grip_sinkhorn_balance(_ptr(p), _ptr(log_target), _ptr(b_in), float(tau), int(iters), n, c, _ptr(q),
+                                           _ptr(pred), _ptr(mass), _ptr(b_out), _ptr(ws), ws.numel(), _stream()))
+    return q, pred, mass, b_out
 
 
 def leaderboard_scan(probs, pred, path_rank, k):

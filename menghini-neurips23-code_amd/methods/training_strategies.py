@@ -86,11 +86,22 @@ class TrainingStrategy:
             self.gmm = pl.TransductiveGMM(k=int(getattr(config, "GMM_K", 3)), lam=float(getattr(config, "GMM_LAMBDA", 1.0)),
                                           iters=int(getattr(config, "GMM_ITERS", 10)), z_iters=int(getattr(config, "GMM_Z_ITERS", 5)),
                                           keep_graphs=self.modality == "text")
+        # BALANCED_PSEUDOLABELS (all modalities, default False): every pseudolabel pass balances its [n, c] matrix -- the head's probabilities, or the Z
+        # of LABEL_PROPAGATION / TRANSDUCTIVE_GMM when one of them is on -- towards a class prior with Sinkhorn-Knopp before the leaderboard scan
+        # (pl.BalancedAssignment; OT_TAU 1.0, OT_ITERS 3, OT_PRIOR None = uniform, else a list of c weights: untuned).  `predict`, validation, the Tip
+        # cache and the adapter do not see it.
+        self.balanced = None
+        if bool(getattr(config, "BALANCED_PSEUDOLABELS", False)):
+            self.balanced = pl.BalancedAssignment(tau=float(getattr(config, "OT_TAU", 1.0)), iters=int(getattr(config, "OT_ITERS", 3)),
+                                                  prior=getattr(config, "OT_PRIOR", None), inner=self.label_prop if self.label_prop is not None else self.gmm)
         self.declare_custom_encoder()
         self.initialize_prompts_parameters()
 
     def transduction(self):
-        """What the pseudolabel passes install with pl.label_propagation(): the LabelPropagation, the TransductiveGMM, or None."""
+        """What the pseudolabel passes install with pl.label_propagation(): the BalancedAssignment (which wraps the LabelPropagation or the
+        TransductiveGMM when one is on), else the LabelPropagation, the TransductiveGMM, or None."""
+        if self.balanced is not None:
+            return self.balanced
         return self.label_prop if self.label_prop is not None else self.gmm
 
     @property

@@ -106,6 +106,10 @@ _SIGS = {
     "grip_gmm_estep_workspace": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
     "grip_gmm_estep": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                c_void_p, c_void_p, c_size_t, c_void_p]),
+    # (ABI 9 additions) balanced (Sinkhorn-Knopp) assignment of a pool's probabilities to a class prior (csrc/sinkhorn.hip)
+    "grip_sinkhorn_workspace": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "grip_sinkhorn_balance": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
     "grip_preprocess_image": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                       c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "grip_preprocess_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -1005,20 +1005,60 @@ class TransductiveGMM(_PoolGraph):
         return f"TransductiveGMM(k={self.k}, lam={self.lam}, iters={self.iters}, z_iters={self.z_iters}, var_floor={self.var_floor})"
 
 
+class BalancedAssignment:
+    """Settings of the balanced pseudolabel pass (off unless installed by label_propagation()): the pool's [n, c] probabilities are treated as an
+    optimal-transport problem -- every row sums to one, every class receives the share `prior` gives it (None: the same share) -- and `iters`
+    Sinkhorn-Knopp iterations are run on probs ** tau (engine.sinkhorn_balance; Cuturi 2013; SeLa, Asano et al. 2020; SwAV, Caron et al. 2020).  The
+    leaderboard scan then ranks by the balanced Q and its arg-max, so a class the head is biased against is filled with the rows that lean towards it
+    most instead of with other classes' overflow.  No epsilon-scaled cost, no stopping rule: `iters` is how hard the balance is pressed.  inner: None,
+    a LabelPropagation or a TransductiveGMM whose Z is balanced instead of the head's probabilities.  prior: None or c finite positive weights (a list
+    or a tensor).  The defaults are untuned.  After a pass `state` holds the last (mass [c], log_scale [c])."""
+
+    def __init__(self, tau=1.0, iters=3, prior=None, inner=None):
+        self.tau, self.iters = float(tau), int(iters)
+        if not 0.0 < self.tau < float("inf"):
+            raise ValueError(f"BalancedAssignment: tau = {tau} (a finite tau > 0)")
+        if self.iters < 0:
+            raise ValueError(f"BalancedAssignment: iters = {iters} (at least 0)")
+        if prior is not None:
+            prior = torch.as_tensor(prior, dtype=torch.float64).detach().cpu()
+            if prior.dim() != 1 or prior.numel() < 1 or not bool((torch.isfinite(prior) & (prior > 0)).all()):
+                raise ValueError(f"BalancedAssignment: prior must be a list of finite positive weights, one per class, got {prior.tolist()}")
+        self.prior = prior
+        if inner is not None and not isinstance(inner, (LabelPropagation, TransductiveGMM)):
+            raise ValueError(f"BalancedAssignment: inner must be a LabelPropagation, a TransductiveGMM or None, got {type(inner).__name__}")
+        self.inner = inner
+        self.infix = "ot_" + (inner.infix if inner is not None else "")       # of the pseudolabel pickle's name: ot_, ot_lp_, ot_gmm_
+        self.state = None           # (mass [c], log_scale [c]) of the most recent pass
+
+    def transduce(self, img_emb, probs, paths=None):
+        """(Q, pred) of the pool: the balanced assignment of inner's Z (of probs without an inner) and its first arg-max."""
+        z = probs if self.inner is None else self.inner.transduce(img_emb, probs, paths)[0]
+        if self.prior is not None and self.prior.numel() != z.shape[1]:
+            raise ValueError(f"BalancedAssignment: a prior of {self.prior.numel()} weights for {z.shape[1]} classes")
+        q, pred, mass, log_scale = engine.sinkhorn_balance(z, self.tau, self.iters, self.prior)
+        self.state = (mass, log_scale)
+        return q, pred
+
+    def __repr__(self):
+        return f"BalancedAssignment(tau={self.tau}, iters={self.iters}, prior={'None' if self.prior is None else 'given'}, inner={self.inner})"
+
+
 _PROPAGATION = []   # settings installed by label_propagation(), innermost last.  Empty unless a caller opened one: every pass is per-image by default
 
 
 @contextlib.contextmanager
 def label_propagation(lp):
-    """Install `lp` (a LabelPropagation or a TransductiveGMM, or None: no-op) for the pseudolabel passes underneath -- how it reaches the
-    reference-named compute_pseudo_labels / pseudolabel_top_k, whose signatures are the reference's.  While one is installed pseudolabel_from_features
-    transduces with it, the callers that would pick identical_lists take their plain branch (no reference list can be identical to a transduced one) and
-    pseudolabel_top_k names its pickle after the object's `infix`: `..._pseudolabels_lp_split_...` / `..._pseudolabels_gmm_split_...`."""
+    """Install `lp` (a LabelPropagation, a TransductiveGMM or a BalancedAssignment, or None: no-op) for the pseudolabel passes underneath -- how it
+    reaches the reference-named compute_pseudo_labels / pseudolabel_top_k, whose signatures are the reference's.  While one is installed
+    pseudolabel_from_features transduces with it, the callers that would pick identical_lists take their plain branch (no reference list can be identical
+    to a transduced one) and pseudolabel_top_k names its pickle after the object's `infix`: `..._pseudolabels_lp_split_...` /
+    `..._pseudolabels_gmm_split_...` / `..._pseudolabels_ot_split_...` (`ot_lp_`, `ot_gmm_` with an inner transduction)."""
     if lp is None:
         yield None
         return
-    if not isinstance(lp, (LabelPropagation, TransductiveGMM)):
-        raise TypeError(f"label_propagation: expected a LabelPropagation, a TransductiveGMM or None, got {type(lp).__name__}")
+    if not isinstance(lp, (LabelPropagation, TransductiveGMM, BalancedAssignment)):
+        raise TypeError(f"label_propagation: expected a LabelPropagation, a TransductiveGMM, a BalancedAssignment or None, got {type(lp).__name__}")
     _PROPAGATION.append(lp)
     try:
         yield lp
@@ -1027,7 +1067,7 @@ def label_propagation(lp):
 
 
 def propagation():
-    """The innermost installed LabelPropagation / TransductiveGMM, or None."""
+    """The innermost installed LabelPropagation / TransductiveGMM / BalancedAssignment, or None."""
     return _PROPAGATION[-1] if _PROPAGATION else None
 
 

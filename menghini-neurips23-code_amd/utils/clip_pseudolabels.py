@@ -104,7 +104,7 @@ def compute_pseudo_labels(k, template, dataset, classnames, transform, clip_mode
 
 def pseudolabel_top_k(config, data_name, k, template, dataset, classnames, transform, clip_model, label_to_idx, device,
                       vis_encoder, split_seed):
-    # a propagated list ("lp_"), a GMM list ("gmm_") and a reference-style one never share a cache file
+    # a propagated list ("lp_"), a GMM list ("gmm_"), a balanced one ("ot_", "ot_lp_", "ot_gmm_") and a reference-style one never share a cache file
     lp = pl.propagation().infix if pl.propagation() is not None else ""
     filename = f"pseudolabels/{data_name}_{vis_encoder.replace('/', '')}_{config.LEARNING_PARADIGM}_{config.MODEL}_{k}_pseudolabels_{lp}split_{split_seed}.pickle"
     if os.path.exists(filename):
