@@ -434,6 +434,30 @@ int grip_sinkhorn_balance(const float* probs, const float* log_target, const flo
                           int32_t* pred, float* mass, float* log_scale_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Weighted cross-entropy against soft targets gathered from a pool's assignment matrix (ABI 9 addition; csrc/soft_ce.hip): grip_weighted_ce for
+ * prompt steps that train on the row of Z (label propagation, transductive GMM) or Q (Sinkhorn balance) behind a pseudolabel instead of its arg-max.
+ *   logits [n, c], labels [n] int32, row_weight [n]: as grip_weighted_ce.
+ *   soft [soft_rows, cz] f32: the matrix, read in place (NULL: every row is a hard row; soft_row and col_map may then be NULL).
+ *   soft_row [n] int32: the matrix row of batch row i; a value < 0 or >= soft_rows marks a HARD row, whose target is onehot(labels[i]).
+ *   col_map [cz] int32: the logits column of every matrix column -- distinct entries in [0, c) (the caller's contract; an entry outside [0, c) is
+ *   skipped, never indexed).
+ * Target of a soft row r:  L_j = inv_temperature logf(max(soft[r, j], 2^-126)),  s = softmax_j(L)  (the floor and log-domain form of
+ * grip_sinkhorn_balance: soft ** inv_temperature renormalised; an all-zero matrix row is uniform over the cz mapped columns), s_j placed at column
+ * col_map[j], every other column 0.  Every row:  t = (1 - smoothing) s + smoothing / c,  T = sum_c t_c,
+ *   loss = sum over the rows with w_i != 0 of  w_i (T_i lse_i - sum_c t_ic x_ic),        grad_i = w_i (T_i softmax(x_i) - t_i),
+ * target_out [n, c] f32 (optional) receives t.  A hard row whose label lies outside [0, c) keeps grip_weighted_ce's rule: it is left out of the loss,
+ * no one-hot is subtracted (s = 0, t = smoothing / c) and the whole softmax stays, grad_i = w_i (softmax(x_i) - t_i) -- T_i is taken as 1 there; with
+ * smoothing == 0 that is w_i softmax(x_i).  loss [1]; grad_logits and target_out may each be NULL.
+ * With soft == NULL and smoothing == 0, loss and every gradient element are bit-equal to grip_weighted_ce on the same operands: hard rows without
+ * smoothing run that kernel's arithmetic and the loss partials are added in its order.  No atomics, no scratch, no workspace; two calls are bit-equal;
+ * a row's gradient and target bits depend on that row, its matrix row and col_map alone (not on n, its place in the batch or the other rows).
+ * Refused with nothing written: a null operand, n or c <= 0, cz outside [1, c] with soft given, inv_temperature not finite or <= 0, smoothing outside
+ * [0, 1), and c > 16000 with soft given (the inverse of col_map is held in the LDS). */
+int grip_soft_ce(const float* logits, const int32_t* labels, const float* row_weight, int n, int c, const float* soft, int64_t soft_rows, int cz,
+                 const int32_t* soft_row, const int32_t* col_map, float inv_temperature, float smoothing, float* loss, float* grad_logits,
+                 float* target_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CLIP preprocessing of one decoded image: the `_transform` the reference applies per item on the host
  * (data/dataset.py:64-79 via clip.load's preprocess): Resize(n_px, BICUBIC) -> CenterCrop(n_px) -> ToTensor -> Normalize.
  * Bit-exact with Pillow's 8-bit bicubic resample; only the cropped rows / columns are produced.

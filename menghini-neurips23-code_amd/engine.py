@@ -584,6 +584,83 @@ class WeightedCEFn(torch.autograd.Function):
         return grad * g, None, None
 
 
+_COL_MAPS_OK = []       # [(weakref of a col_map tensor, its version counter, c)] that passed the host check of soft_ce, most recent first
+
+
+def _check_col_map(col_map, c):
+    """col_map (int32 [cz] on the device) is injective into [0, c): checked on the host ONCE per tensor (and per version of it) -- a later call with the
+    same tensor costs no device read, so a step may run under graph capture once its warm-up has passed here."""
+    import weakref
+    for ref, version, cc in _COL_MAPS_OK:
+        held = ref()        # (alive: its memory has not been handed to another tensor since the check)
+        if held is not None and held.data_ptr() == col_map.data_ptr() and held.numel() == col_map.numel() and version == col_map._version and cc == c:
+            return
+    host = col_map.cpu()
+    if host.numel() and (int(host.min()) < 0 or int(host.max()) >= c or torch.unique(host).numel() != host.numel()):
+        raise native.GripError(f"soft_ce: col_map must hold distinct logits columns in [0, {c}), got {host.tolist()}")
+    _COL_MAPS_OK.insert(0, (weakref.ref(col_map), col_map._version, c))
+    del _COL_MAPS_OK[8:]
+
+
+def soft_ce(logits, labels, row_weight, soft=None, soft_row=None, col_map=None, temperature=1.0, smoothing=0.0, want_target=False):
+    """(loss, grad[, target]) of the weighted cross-entropy against soft targets (csrc/soft_ce.hip, grip_soft_ce): batch row i with
+    0 <= soft_row[i] < soft.shape[0] trains on softmax((1 / temperature) log max(soft[soft_row[i]], 2^-126)) scattered to the logits columns
+    col_map[j], every other row on onehot(labels[i]); every target is smoothed, t = (1 - smoothing) s + smoothing / c.  loss: 0-d f32,
+    sum_i w_i (T_i lse_i - <t_i, x_i>); grad [n, c] = w_i (T_i softmax(x_i) - t_i); target [n, c] = t with want_target.  `soft` (f32 [rows, cz]) is read in
+    place: no [n, c] target block is built on the host.  soft=None with smoothing 0 gives grip_weighted_ce's bits.  No autograd (SoftCEFn)."""
+    lib = native.lib()
+    if not torch.is_tensor(logits) or logits.dim() != 2 or not logits.is_cuda:
+        raise native.GripError(f"soft_ce: logits must be a [n, c] tensor on the GPU, got {getattr(logits, 'shape', type(logits))}")
+    lg = logits.detach().contiguous().float()
+    n, c = lg.shape
+    dev = lg.device
+    if not torch.is_tensor(labels) or tuple(labels.shape) != (n,) or labels.dtype.is_floating_point:
+        raise native.GripError(f"soft_ce: labels must be an integer [{n}] tensor, got {getattr(labels, 'shape', type(labels))} {getattr(labels, 'dtype', None)}")
+    if not torch.is_tensor(row_weight) or tuple(row_weight.shape) != (n,) or not row_weight.dtype.is_floating_point:
+        raise native.GripError(f"soft_ce: row_weight must be a floating-point [{n}] tensor, got {getattr(row_weight, 'shape', type(row_weight))}")
+    lab = labels.to(device=dev, dtype=torch.int32).contiguous()
+    w = row_weight.to(device=dev, dtype=torch.float32).contiguous()
+    rows = cz = 0
+    if soft is not None:
+        if not torch.is_tensor(soft) or soft.dim() != 2 or soft.dtype != torch.float32 or soft.device != dev or not soft.is_contiguous():
+            raise native.GripError(f"soft_ce: soft must be a contiguous float32 [rows, cz] tensor on {dev} (it is read in place), got "
+                                   f"{getattr(soft, 'shape', type(soft))} {getattr(soft, 'dtype', None)} on {getattr(soft, 'device', None)}")
+        rows, cz = soft.shape
+        soft_row = _gmm_operand("soft_ce", "soft_row", soft_row, (n,), lg, torch.int32)
+        if not torch.is_tensor(col_map) or tuple(col_map.shape) != (cz,) or col_map.dtype != torch.int32 or col_map.device != dev or not col_map.is_contiguous():
+            raise native.GripError(f"soft_ce: col_map must be a contiguous int32 [{cz}] tensor on {dev}, got {getattr(col_map, 'shape', type(col_map))} "
+                                   f"{getattr(col_map, 'dtype', None)}")
+        if not 1 <= cz <= c:
+            raise native.GripError(f"soft_ce: soft has {cz} columns for {c} logits columns (1 .. c)")
+        _check_col_map(col_map, c)
+    else:
+        soft_row = col_map = None
+    if not 0.0 < float(temperature) < float("inf"):
+        raise native.GripError(f"soft_ce: temperature = {temperature} (a finite temperature > 0)")
+    loss = torch.zeros(1, dtype=torch.float32, device=dev)
+    grad = torch.empty_like(lg)
+    target = torch.empty_like(lg) if want_target else None
+    native.check(lib.grip_soft_ce(_ptr(lg), _ptr(lab), _ptr(w), n, c, _ptr(soft), rows, cz, _ptr(soft_row), _ptr(col_map), 1.0 / float(temperature),
+                                  float(smoothing), _ptr(loss), _ptr(grad), _ptr(target), _stream()))
+    return (loss[0], grad, target) if want_target else (loss[0], grad)
+
+
+class SoftCEFn(torch.autograd.Function):
+    """WeightedCEFn's twin on soft targets: sum_i w_i CE(logits_i, t_i) with t of engine.soft_ce, native forward + backward (one kernel produces both).
+    apply(logits, labels, row_weight, soft, soft_row, col_map, temperature, smoothing)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, row_weight, soft, soft_row, col_map, temperature, smoothing):
+        loss, grad = soft_ce(logits, labels, row_weight, soft, soft_row, col_map, temperature, smoothing)
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad * g,) + (None,) * 7
+
+
 class UptMixerFn(torch.autograd.Function):
     """UPTModel's prompt mixer (models/prompts_models.py:129-146) on the native kernels (csrc/mixer.hip): forward and the
     gradients of all 22 tensors -- the two prompt embeddings, the four projections and the one-block transformer.  A 23rd tensor,

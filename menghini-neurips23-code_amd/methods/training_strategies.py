@@ -94,6 +94,22 @@ class TrainingStrategy:
         if bool(getattr(config, "BALANCED_PSEUDOLABELS", False)):
             self.balanced = pl.BalancedAssignment(tau=float(getattr(config, "OT_TAU", 1.0)), iters=int(getattr(config, "OT_ITERS", 3)),
                                                   prior=getattr(config, "OT_PRIOR", None), inner=self.label_prop if self.label_prop is not None else self.gmm)
+        # SOFT_PSEUDOLABELS (all modalities, default False; SOFT_TEMPERATURE 1.0: untuned): every pseudolabelled row of a prompt step trains on its
+        # sharpened row of the matrix the pass ranked (Z or Q; pl.SoftTargetStore -> engine.soft_ce) instead of the one-hot of its pseudolabel; labelled
+        # rows keep their one-hot.  It needs one of the three transductions above: the per-image pass has no device matrix to offer.  LABEL_SMOOTHING
+        # (default 0.0) smooths every row's target and works on its own.  row_weights, the epoch accuracy, the held-out pseudolabel validation, `predict`,
+        # the Tip cache and the adapter (hard labels) do not see either.
+        self.soft_store, self.soft_temperature = None, float(getattr(config, "SOFT_TEMPERATURE", 1.0))
+        self.label_smoothing = float(getattr(config, "LABEL_SMOOTHING", 0.0))
+        if not 0.0 <= self.label_smoothing < 1.0:
+            raise ValueError(f"LABEL_SMOOTHING: {self.label_smoothing} (0 <= LABEL_SMOOTHING < 1)")
+        if bool(getattr(config, "SOFT_PSEUDOLABELS", False)):
+            if self.transduction() is None:
+                raise ValueError("SOFT_PSEUDOLABELS needs LABEL_PROPAGATION, TRANSDUCTIVE_GMM or BALANCED_PSEUDOLABELS: only a transduced pass keeps the "
+                                 "matrix it ranked on the device")
+            if not 0.0 < self.soft_temperature < float("inf"):
+                raise ValueError(f"SOFT_TEMPERATURE: {self.soft_temperature} (a finite temperature > 0)")
+            self.soft_store = pl.SoftTargetStore()
         self.declare_custom_encoder()
         self.initialize_prompts_parameters()
 
@@ -296,7 +312,7 @@ class TrainingStrategy:
         c = self.config
         pseudo_classes = self.classes if self.paradigm in ("ssl", "ul") else self.unseen_classes
         # the frozen-CLIP pass runs the same towers over the same pool as the trained-prompt passes after it
-        with pl.pool_cache(self.pool_cache), pl.label_propagation(self.transduction()):
+        with pl.pool_cache(self.pool_cache), pl.label_propagation(self.transduction()), pl.soft_targets(self.soft_store):
             pseudolabel_top_k(c, c.DATASET_NAME, int(c.N_PSEUDOSHOTS), self.template, unlabeled_data, pseudo_classes, self.transform,
                               self.clip_model, self.label_to_idx, self.device, c.VIS_ENCODER, getattr(c, "SPLIT_SEED", 0))
         return self.merge_pseudolabels(train_data, unlabeled_data)
@@ -339,6 +355,28 @@ class TrainingStrategy:
         unseen_ids = {self.label_to_idx[c] for c in self.unseen_classes}   # membership by label id (transductive_zsl/textual_fpl.py:117-147)
         return steps.fpl_row_weights([int(l) in unseen_ids for l in labels], gamma_seen=1.0, gamma_pseudo=self.balance_param)
 
+    def soft_targets(self, classes, only_seen=False):
+        """The steps.SoftTargets of an epoch over `classes`, or None (both switches absent: the steps call WeightedCEFn exactly as before).  The matrix
+        is the one the last pseudolabel pass recorded (SOFT_PSEUDOLABELS; none for only_seen training, which has no pseudolabelled rows, and before a
+        pass has recorded one); LABEL_SMOOTHING alone gives a SoftTargets without a matrix."""
+        store = None if only_seen else self.soft_store
+        if store is not None and store.matrix is not None:
+            ids = [self.label_to_idx[c] for c in classes]
+            return steps.SoftTargets(store.matrix, store.col_map(ids), self.soft_temperature, self.label_smoothing)
+        return steps.SoftTargets(smoothing=self.label_smoothing) if self.label_smoothing > 0.0 else None
+
+    def soft_rows(self, soft, labels, names):
+        """int32 [B] on the device: the matrix row of every PSEUDOLABELLED row of the batch -- membership as row_weights decides it: by file name in
+        check_unlabeled (ssl, ul), by an unseen label id (trzsl) -- and -1 for the labelled rows, which keep their one-hot.  None without a matrix."""
+        if soft is None or soft.matrix is None:
+            return None
+        if self.paradigm == "trzsl":
+            unseen_ids = {self.label_to_idx[c] for c in self.unseen_classes}
+            pseudo = [int(l) in unseen_ids for l in labels]
+        else:
+            pseudo = [n in self.check_unlabeled for n in names]
+        return self.soft_store.rows(list(names), hard=[not p for p in pseudo])      # (built on the host, one upload: no synchronisation)
+
     # ------------------------------------------------------------------ loops
     def _loader(self, data, shuffle):
         """Data-parallel like the reference under `accelerate launch` (methods_config/accelerate_config.yml: MULTI_GPU): every rank gets its OWN
@@ -359,19 +397,20 @@ class TrainingStrategy:
         lut[idx] = torch.arange(len(classes), device=self.device)
         return classes, idx, lut
 
-    def _graphed_step(self, classes):
+    def _graphed_step(self, classes, soft=None):
         """The HIP-graph replay of this strategy's prompt step (steps.Graphed*Step) for the current model and class list; rebuilt
-        whenever define_model made a new model / optimizer."""
-        key = (self._model_gen, tuple(classes))
+        whenever define_model made a new model / optimizer, or the soft targets' key moved (another matrix buffer, temperature or smoothing)."""
+        key = (self._model_gen, tuple(classes)) if soft is None else (self._model_gen, tuple(classes), soft.key())
         if getattr(self, "_gkey", None) != key:
+            kw = {} if soft is None else {"soft": soft}
             if self.modality == "text":
                 self.model.classes = classes
-                g = steps.GraphedCoopFeatureStep(self.model, self.clip_model, self.optimizer)
+                g = steps.GraphedCoopFeatureStep(self.model, self.clip_model, self.optimizer, **kw)
             elif self.modality == "image":
-                g = steps.GraphedVptStep(self.model, self.fixed_text_features(classes), self.scale(), self.optimizer)
+                g = steps.GraphedVptStep(self.model, self.fixed_text_features(classes), self.scale(), self.optimizer, **kw)
             else:
                 self.model.classes = classes
-                g = steps.GraphedUptStep(self.model, self.scale(), self.optimizer)
+                g = steps.GraphedUptStep(self.model, self.scale(), self.optimizer, **kw)
             self._gkey, self._gstep = key, g
         return self._gstep
 
@@ -408,9 +447,10 @@ class TrainingStrategy:
             self.model.classes = classes
         accum = int(getattr(self.config, "ACCUMULATION_ITER", 1))
         aug = self.view_sampler()
+        soft = self.soft_targets(classes, only_seen)
         if accum != 1 or not getattr(self.config, "GRAPH_STEPS", True):
-            return self._train_epoch_eager(train_loader, classes, ids, lut, accum, aug, epoch)
-        g = self._graphed_step(classes)
+            return self._train_epoch_eager(train_loader, classes, ids, lut, accum, aug, epoch, soft)
+        g = self._graphed_step(classes, soft)
         total = torch.zeros((), dtype=torch.float64, device=self.device)      # the sum the eager loop forms in Python doubles
         correct = torch.zeros((), dtype=torch.int64, device=self.device)
         count = 0
@@ -421,18 +461,19 @@ class TrainingStrategy:
                 img = img.to(self.device, non_blocking=True)
                 if aug is not None:
                     img = aug.batch(img.contiguous(), names, epoch)
-                yield img, label.to(self.device, non_blocking=True), w.to(self.device, non_blocking=True), list(names)
+                rows = self.soft_rows(soft, label.tolist(), names)   # (None without a soft-target matrix)
+                yield img, label.to(self.device, non_blocking=True), w.to(self.device, non_blocking=True), list(names), rows
 
         if self.modality == "text":
             if aug is None and getattr(self.config, "CACHE_FROZEN_FEATURES", True):
-                stream = ((self.frozen_image_features(img, names), label, w) for img, label, w, names in batches())
+                stream = ((self.frozen_image_features(img, names), label, w, rows) for img, label, w, names, rows in batches())
             else:           # every image is encoded every time it is used, a group of batches per frozen-tower forward
-                stream = steps.lookahead_image_features(self.clip_model, ((img, label, w) for img, label, w, _ in batches()),
+                stream = steps.lookahead_image_features(self.clip_model, ((img, label, w, rows) for img, label, w, _, rows in batches()),
                                                         int(getattr(self.config, "IMAGE_LOOKAHEAD", 51)))
         else:
-            stream = ((img, label, w) for img, label, w, _ in batches())
-        for x, label, w in stream:
-            total += g(x, lut[label], w)
+            stream = ((img, label, w, rows) for img, label, w, _, rows in batches())
+        for x, label, w, rows in stream:
+            total += g(x, lut[label], w) if rows is None else g(x, lut[label], w, rows)
             correct += (ids[g.logits.argmax(1)] == label).sum()
             count += len(label)
         self.update_scheduler()
@@ -446,7 +487,7 @@ class TrainingStrategy:
         total, correct, count, n_batches = t.tolist()
         return total / max(n_batches, 1.0), correct / max(count, 1.0)
 
-    def _train_epoch_eager(self, train_loader, classes, ids, lut, accum, aug=None, epoch=0):
+    def _train_epoch_eager(self, train_loader, classes, ids, lut, accum, aug=None, epoch=0, soft=None):
         total, correct, count = 0.0, 0, 0
         for i, (img, _, _, label, names) in enumerate(train_loader):
             img, label = img.to(self.device), label.to(self.device)
@@ -455,7 +496,7 @@ class TrainingStrategy:
             image_features, text_features = self.features(img, classes, None if aug is not None else list(names))      # views are never cached by name
             logits = steps.CosineHeadFn.apply(image_features, text_features, self.scale())
             w = self.row_weights(label.tolist(), names).to(self.device)
-            loss = steps.WeightedCEFn.apply(logits, lut[label], w) / accum
+            loss = steps.step_loss(logits, lut[label], w, soft, self.soft_rows(soft, label.tolist(), names)) / accum
             loss.backward()
             total += float(loss.detach()) * accum
             if (i + 1) % accum == 0 or i + 1 == len(train_loader):
@@ -719,7 +760,7 @@ class TrainingStrategy:
         images = _pool_images(unlabeled_data, self.transform, self.device)
         labels = [self.label_to_idx[c] for c in classes]
         paths = list(unlabeled_data.filepaths)      # the pool as passed to the pass (grip_train resets it to the original list every iteration): the cache's key
-        with pl.pool_cache(self.pool_cache), pl.label_propagation(self.transduction()):        # (None: nothing is installed)
+        with pl.pool_cache(self.pool_cache), pl.label_propagation(self.transduction()), pl.soft_targets(self.soft_store):       # (None: nothing is installed)
             if pl.propagation() is not None:
                 log.info(f"{pl.propagation()} is installed: the pass propagates over the pool and takes the plain branch (no reference list to be identical to)")
             if pl.mode() == "identical" and pl.propagation() is None and not self.clip_model.exact:

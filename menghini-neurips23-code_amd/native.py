@@ -110,6 +110,9 @@ _SIGS = {
     "grip_sinkhorn_workspace": (c_int, [c_int, c_int, POINTER(c_size_t)]),
     "grip_sinkhorn_balance": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                       c_void_p]),
+    # (ABI 9 addition) weighted cross-entropy against soft targets gathered from a pool's assignment matrix (csrc/soft_ce.hip)
+    "grip_soft_ce": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p,
+                             c_void_p, c_void_p]),
     "grip_preprocess_image": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                       c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "grip_preprocess_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -1071,14 +1071,121 @@ def propagation():
     return _PROPAGATION[-1] if _PROPAGATION else None
 
 
+# ------------------------------------------------------------------------------------------ from the pass to the step: the matrix behind the lists
+class SoftTargetStore:
+    """Keeps the device matrix a transduced pseudolabel pass ranked (Z of LabelPropagation / TransductiveGMM, Q of BalancedAssignment) so that the
+    prompt steps can train on the ROW behind a pseudolabel instead of its arg-max (engine.soft_ce; off unless installed by soft_targets()).
+    record() is called by pseudolabel_from_features; the steps ask for
+      rows(names)         the matrix row of every file name of a batch (int32 on the matrix's device), -1 for a name that is not in the pool.  Names are
+                          BASE names: the dataset hands those out and the strategies' check_unlabeled is keyed by them; a base name that names two pool
+                          rows raises when it is asked about;
+      col_map(class_ids)  int32 [cz]: the position, in a step's training class list (label ids), of every class the pass ranked -- TRZSL ranks over
+                          the unseen classes and trains over all of them.
+    The store OWNS its buffer: the first record() copies the matrix into it and every later one of the same shape and device overwrites it in place,
+    so the address a captured graph read the matrix from stays valid and the next replay trains on the new pass (steps.GraphedStep).  Another shape
+    allocates another buffer (a graphed step sees its key move and runs eagerly until it is rebuilt).  Multi-rank runs need nothing: every rank
+    ranks the same gathered pool."""
+
+    def __init__(self):
+        self.matrix = None          # f32 [n, cz] on the device, or None before the first pass
+        self.class_labels = ()      # the label id of every matrix column
+        self.records = 0
+        self._row_of = {}           # base name -> pool row, or -2 for a base name that occurs twice
+        self._col_maps = {}         # tuple(training label ids) -> int32 [cz] device tensor (one tensor per list: a fixed address, checked once)
+
+    def record(self, paths, class_labels, z):
+        if not torch.is_tensor(z) or z.dim() != 2 or z.dtype != torch.float32 or tuple(z.shape) != (len(paths), len(class_labels)):
+            raise ValueError(f"SoftTargetStore.record: a float32 [{len(paths)}, {len(class_labels)}] matrix was expected, got {getattr(z, 'shape', type(z))} "
+                             f"{getattr(z, 'dtype', None)}")
+        z = z.detach()
+        if self.matrix is not None and self.matrix.shape == z.shape and self.matrix.device == z.device:
+            self.matrix.copy_(z)
+        else:
+            self.matrix = z.clone(memory_format=torch.contiguous_format)
+        labels = tuple(int(c) for c in class_labels)
+        if labels != self.class_labels:
+            self.class_labels = labels
+            self._col_maps.clear()
+        self._row_of = {}
+        for i, p in enumerate(paths):
+            name = p.split("/")[-1]
+            self._row_of[name] = -2 if name in self._row_of else i
+        self.records += 1
+
+    def forget(self):
+        """No name is in the pool any more (every row asked about is a hard row); the buffer stays where it is."""
+        self._row_of = {}
+
+    def rows(self, names, hard=None):
+        """int32 [len(names)] on the matrix's device.  hard: optional list of flags, True = do not ask about this name (its row is -1: a labelled row
+        of the batch, whatever it is called)."""
+        if self.matrix is None:
+            raise ValueError("SoftTargetStore.rows: no pass has recorded a matrix yet")
+        out = []
+        for i, n in enumerate(names):
+            if hard is not None and hard[i]:
+                out.append(-1)
+                continue
+            r = self._row_of.get(n.split("/")[-1], -1)
+            if r == -2:
+                raise ValueError(f"SoftTargetStore: the base name {n.split('/')[-1]!r} names two rows of the pool: soft targets are keyed by base names, "
+                                 "as the strategies' check_unlabeled is")
+            out.append(r)
+        return torch.tensor(out, dtype=torch.int32).to(self.matrix.device, non_blocking=True)
+
+    def col_map(self, class_ids):
+        if self.matrix is None:
+            raise ValueError("SoftTargetStore.col_map: no pass has recorded a matrix yet")
+        key = tuple(int(c) for c in class_ids)
+        if key not in self._col_maps:
+            at = {c: i for i, c in enumerate(key)}
+            missing = [c for c in self.class_labels if c not in at]
+            if missing or len(at) != len(key):
+                raise ValueError(f"SoftTargetStore.col_map: the pass ranked classes {missing} that the training class list {list(key)} does not hold "
+                                 "(or that list repeats a class)")
+            self._col_maps[key] = torch.tensor([at[c] for c in self.class_labels], dtype=torch.int32, device=self.matrix.device)
+        return self._col_maps[key]
+
+
+_SOFT_STORES = []   # stores installed by soft_targets(), innermost last.  Empty unless a caller opened one: no pass records anything by default
+
+
+@contextlib.contextmanager
+def soft_targets(store):
+    """Install `store` (a SoftTargetStore, or None: no-op) for the pseudolabel passes underneath, as pool_cache() and label_propagation() install
+    theirs.  While one is installed pseudolabel_from_features records the matrix of every transduced pass in it, and pseudolabel_top_k does not read an
+    existing pickle (a loaded list has no matrix behind it): the pass runs and rewrites the same file."""
+    if store is None:
+        yield None
+        return
+    if not isinstance(store, SoftTargetStore):
+        raise TypeError(f"soft_targets: expected a SoftTargetStore or None, got {type(store).__name__}")
+    _SOFT_STORES.append(store)
+    try:
+        yield store
+    finally:
+        _SOFT_STORES.pop()
+
+
+def soft_target_store():
+    """The innermost installed SoftTargetStore, or None."""
+    return _SOFT_STORES[-1] if _SOFT_STORES else None
+
+
 @torch.no_grad()
 def pseudolabel_from_features(img_emb, txt_emb, scale, paths, class_labels, k, argmax_on="probs"):
     """Head + scan.  argmax_on: "probs" (compute_pseudo_labels, :39) or "logits" (assign_pseudo_labels).  With a LabelPropagation or a
-    TransductiveGMM installed the scan runs on its Z over the whole (gathered, on every rank alike) pool and on arg-max Z, for both forms of argmax_on."""
+    TransductiveGMM installed the scan runs on its Z over the whole (gathered, on every rank alike) pool and on arg-max Z, for both forms of argmax_on;
+    a SoftTargetStore installed by soft_targets() then records that matrix."""
     logits, probs, am_l, am_p = engine.cosine_head(img_emb, txt_emb, scale)
     lp = propagation()
     if lp is not None and img_emb.shape[0] >= 2:        # (a pool of one image has no neighbour to hear from)
         z, z_pred = lp.transduce(img_emb, probs, paths)
+        store = soft_target_store()
+        if store is not None:
+            store.record(paths, class_labels, z)
         return leaderboard(z.cpu().numpy(), z_pred.cpu().numpy(), paths, class_labels, k)
+    if soft_target_store() is not None:
+        soft_target_store().forget()        # a pass without a transduction has no matrix: the rows of an earlier one no longer name its lists
     pred = (am_p if argmax_on == "probs" else am_l).cpu().numpy()
     return leaderboard(probs.cpu().numpy(), pred, paths, class_labels, k)

@@ -9,7 +9,7 @@ import torch
 
 from . import dist as gdist
 from . import engine
-from .engine import CosineHeadFn, WeightedCEFn
+from .engine import CosineHeadFn, SoftCEFn, WeightedCEFn
 
 
 def fpl_row_weights(is_pseudo, gamma_seen=1.0, gamma_pseudo=1.0):
@@ -27,6 +27,38 @@ def fpl_row_weights(is_pseudo, gamma_seen=1.0, gamma_pseudo=1.0):
     if n_p:
         w[is_pseudo] = gamma_pseudo / n_p
     return w
+
+
+class SoftTargets:
+    """What a prompt step needs to train on soft targets (engine.soft_ce): `matrix` f32 [rows, cz] on the device -- the Z or Q a pseudolabel pass ranked,
+    read in place (pseudolabels.SoftTargetStore.matrix) -- `col_map` int32 [cz], the logits column of every matrix column, the sharpening
+    `temperature` and the label `smoothing`.  matrix=None: smoothing alone (every row keeps its one-hot).  A step takes it as `soft=` together with a
+    per-batch `soft_row` int32 [B] (the matrix row of each batch row, -1: a hard row); tip_step and adapter_step keep hard labels."""
+
+    def __init__(self, matrix=None, col_map=None, temperature=1.0, smoothing=0.0):
+        if (matrix is None) != (col_map is None):
+            raise ValueError("SoftTargets: matrix and col_map come together")
+        if not 0.0 < float(temperature) < float("inf"):
+            raise ValueError(f"SoftTargets: temperature = {temperature} (a finite temperature > 0)")
+        if not 0.0 <= float(smoothing) < 1.0:
+            raise ValueError(f"SoftTargets: smoothing = {smoothing} (0 <= smoothing < 1)")
+        self.matrix, self.col_map, self.temperature, self.smoothing = matrix, col_map, float(temperature), float(smoothing)
+
+    def key(self):
+        """What a captured graph depends on: the addresses it read the matrix and the map from, their shapes and the two scalars."""
+        m, c = self.matrix, self.col_map
+        return (None if m is None else (m.data_ptr(), tuple(m.shape), c.data_ptr()), self.temperature, self.smoothing)
+
+
+def step_loss(logits, labels, row_weight, soft=None, soft_row=None):
+    """The loss of a prompt step: WeightedCEFn, exactly as before, without `soft`; SoftCEFn on the rows of soft.matrix that soft_row names with it."""
+    if soft is None:
+        return WeightedCEFn.apply(logits, labels, row_weight)
+    if soft.matrix is None:
+        return SoftCEFn.apply(logits, labels, row_weight, None, None, None, soft.temperature, soft.smoothing)
+    if soft_row is None:
+        raise ValueError("a step with a soft-target matrix needs the batch's soft_row (the matrix row of every batch row, -1 for a hard row)")
+    return SoftCEFn.apply(logits, labels, row_weight, soft.matrix, soft_row, soft.col_map, soft.temperature, soft.smoothing)
 
 
 _SIDE = {}
@@ -54,9 +86,9 @@ def _coop_params(model):
     return [model.prefix] if deep is None else [model.prefix, deep]
 
 
-def coop_step(model, clip_model, images, labels, row_weight, optimizer, image_features=None, return_logits=False):
+def coop_step(model, clip_model, images, labels, row_weight, optimizer, image_features=None, return_logits=False, soft=None, soft_row=None):
     """Textual prompt step: text tower forward+backward over all class prompts, frozen image tower
-    forward only (or cached features)."""
+    forward only (or cached features).  soft / soft_row: SoftTargets and the batch's matrix rows (step_loss); None: hard labels."""
     side = None
     if image_features is None:
         # the frozen image tower does not depend on the prompt: run it on a second stream next to the text
@@ -70,24 +102,24 @@ def coop_step(model, clip_model, images, labels, row_weight, optimizer, image_fe
         torch.cuda.current_stream().wait_stream(side)
         image_features.record_stream(torch.cuda.current_stream())
     logits = CosineHeadFn.apply(image_features, text_features, clip_model.logit_scale.exp().item())
-    loss = WeightedCEFn.apply(logits, labels, row_weight)
+    loss = step_loss(logits, labels, row_weight, soft, soft_row)
     return _finish(loss, _coop_params(model), optimizer, logits if return_logits else None)
 
 
-def vpt_step(model, text_features, logit_scale, images, labels, row_weight, optimizer, return_logits=False):
-    """Visual prompt step: image tower forward+backward; text features fixed for the epoch."""
+def vpt_step(model, text_features, logit_scale, images, labels, row_weight, optimizer, return_logits=False, soft=None, soft_row=None):
+    """Visual prompt step: image tower forward+backward; text features fixed for the epoch.  soft / soft_row: as coop_step."""
     image_features = model(images)
     logits = CosineHeadFn.apply(image_features, text_features, logit_scale)
-    loss = WeightedCEFn.apply(logits, labels, row_weight)
+    loss = step_loss(logits, labels, row_weight, soft, soft_row)
     deep = getattr(model, "deep_prefix", None)      # VPT-Deep: its gradient is all-reduced with the prompt's
     return _finish(loss, [model.prefix] if deep is None else [model.prefix, deep], optimizer, logits if return_logits else None)
 
 
-def upt_step(model, logit_scale, images, labels, row_weight, optimizer, return_logits=False):
-    """Multimodal prompt step: mixer + both towers forward and backward."""
+def upt_step(model, logit_scale, images, labels, row_weight, optimizer, return_logits=False, soft=None, soft_row=None):
+    """Multimodal prompt step: mixer + both towers forward and backward.  soft / soft_row: as coop_step."""
     text_features, image_features = model(images, model.classes)
     logits = CosineHeadFn.apply(image_features, text_features, logit_scale)
-    loss = WeightedCEFn.apply(logits, labels, row_weight)
+    loss = step_loss(logits, labels, row_weight, soft, soft_row)
     return _finish(loss, [p for p in model.parameters() if p.requires_grad], optimizer, logits if return_logits else None)
 
 
@@ -100,13 +132,20 @@ class GraphedStep:
 
     Static inputs: images [B,3,R,R] / labels [B] / row weights [B] are copied into fixed buffers before each replay; the
     trainable parameters are read in place, their .grad buffers are written in place.  Subclasses give `forward_logits`
-    (static inputs -> logits), `params` and the eager fallback."""
+    (static inputs -> logits), `params` and the eager fallback.
 
-    def __init__(self, optimizer):
+    soft (a SoftTargets, the prompt steps only): the loss is step_loss on it, and the step is called with a fourth argument soft_row [B] that is copied
+    into one more static int32 buffer.  The graph captures the ADDRESSES of soft.matrix and soft.col_map: a pass that writes a new matrix of the same
+    shape into the same buffer (pseudolabels.SoftTargetStore.record does) is what the next replay trains on; a SoftTargets whose key() moved --
+    another buffer, shape, temperature or smoothing -- is a batch of "another shape" and runs the eager step."""
+
+    def __init__(self, optimizer, soft=None):
         self.optimizer = optimizer
+        self.soft = soft
         self.graph = None
         self.key = None
         self._pins = []
+        self.r = self._soft_row = None
 
     def __del__(self):
         try:
@@ -127,18 +166,27 @@ class GraphedStep:
     def shape_key(self, images):
         return (tuple(images.shape), images.dtype)
 
+    def _key(self, images):
+        key = self.shape_key(images)
+        return key if self.soft is None else key + (self.soft.key(),)
+
+    def _wants_rows(self):
+        return self.soft is not None and self.soft.matrix is not None
+
     # -- machinery
     def _body(self):
         logits = self.forward_logits()
         self.logits = logits.detach()      # [B, C] of the step just run (a static buffer of the graph; the eager fallback's own tensor)
-        loss = WeightedCEFn.apply(logits, self.y, self.w)
+        loss = step_loss(logits, self.y, self.w, self.soft, self.r)
         loss.backward()
         return loss.detach()
 
-    def _capture(self, images, labels, row_weight):
+    def _capture(self, images, labels, row_weight, soft_row=None):
         dev = images.device
         self.x, self.y, self.w = images.clone(), labels.to(torch.int32).clone(), row_weight.to(torch.float32).clone()
-        self.key = self.shape_key(images)
+        if self._wants_rows():
+            self.r = soft_row.to(device=dev, dtype=torch.int32).clone()
+        self.key = self._key(images)
         ps = self.params()
         warm = torch.cuda.Stream(device=dev)
         warm.wait_stream(torch.cuda.current_stream())
@@ -164,10 +212,13 @@ class GraphedStep:
                 p.grad = torch.zeros_like(p)
         self.grads = [p.grad for p in ps]
 
-    def __call__(self, images, labels, row_weight):
+    def __call__(self, images, labels, row_weight, soft_row=None):
+        if self._wants_rows() and soft_row is None:
+            raise ValueError("a graphed step with a soft-target matrix needs the batch's soft_row")
+        self._soft_row = soft_row                  # (what the eager fallback passes on)
         if self.graph is None:
-            self._capture(images, labels, row_weight)
-        if self.shape_key(images) != self.key:
+            self._capture(images, labels, row_weight, soft_row)
+        if self._key(images) != self.key:
             for p in self.params():
                 p.grad = None                      # (the graph's gradient buffers hold the previous replay's values)
             loss, self.logits = self.eager(images, labels, row_weight)
@@ -175,6 +226,8 @@ class GraphedStep:
         self.x.copy_(images)
         self.y.copy_(labels)
         self.w.copy_(row_weight)
+        if self.r is not None:
+            self.r.copy_(soft_row)
         for p, g in zip(self.params(), self.grads):
             p.grad = g
         self.graph.replay()
@@ -188,8 +241,8 @@ class GraphedCoopStep(GraphedStep):
     """coop_step (textual prompt: text tower forward + backward, frozen image tower on a side stream) replayed from a HIP graph.  A model with deep
     prompts (deep CoOp, model.deep_prefix) has them captured as one more static parameter."""
 
-    def __init__(self, model, clip_model, optimizer):
-        super().__init__(optimizer)
+    def __init__(self, model, clip_model, optimizer, soft=None):
+        super().__init__(optimizer, soft)
         self.model, self.clip_model = model, clip_model
         self.scale = clip_model.logit_scale.exp().item()
 
@@ -209,15 +262,15 @@ class GraphedCoopStep(GraphedStep):
         return CosineHeadFn.apply(image_features, text_features, self.scale)
 
     def eager(self, images, labels, row_weight):
-        return coop_step(self.model, self.clip_model, images, labels, row_weight, self.optimizer, return_logits=True)
+        return coop_step(self.model, self.clip_model, images, labels, row_weight, self.optimizer, return_logits=True, soft=self.soft, soft_row=self._soft_row)
 
 
 class GraphedCoopFeatureStep(GraphedStep):
     """coop_step on image features that were encoded ahead (lookahead_image_features): the text tower's forward + backward, the
     cosine head and the loss, replayed from a HIP graph; the static input is the feature block [B, embed_dim]."""
 
-    def __init__(self, model, clip_model, optimizer):
-        super().__init__(optimizer)
+    def __init__(self, model, clip_model, optimizer, soft=None):
+        super().__init__(optimizer, soft)
         self.model, self.clip_model = model, clip_model
         self.scale = clip_model.logit_scale.exp().item()
 
@@ -231,7 +284,8 @@ class GraphedCoopFeatureStep(GraphedStep):
         return CosineHeadFn.apply(self.x, self.model(self.model.classes), self.scale)
 
     def eager(self, feats, labels, row_weight):
-        return coop_step(self.model, self.clip_model, None, labels, row_weight, self.optimizer, image_features=feats, return_logits=True)
+        return coop_step(self.model, self.clip_model, None, labels, row_weight, self.optimizer, image_features=feats, return_logits=True, soft=self.soft,
+                         soft_row=self._soft_row)
 
 
 def lookahead_overlap():
@@ -319,8 +373,8 @@ class GraphedVptStep(GraphedStep):
     captures a shared prompt ([P, d] / [1, P, d]), with its deep prompts (VPT-Deep, model.deep_prefix [D, P, d]) as one more static parameter when
     the model has them; a model whose prompt is per image ([B, P, d]) runs the eager step."""
 
-    def __init__(self, model, text_features, logit_scale, optimizer):
-        super().__init__(optimizer)
+    def __init__(self, model, text_features, logit_scale, optimizer, soft=None):
+        super().__init__(optimizer, soft)
         self.model, self.text_features, self.scale = model, text_features, float(logit_scale)
 
     def params(self):
@@ -330,22 +384,24 @@ class GraphedVptStep(GraphedStep):
     def forward_logits(self):
         return CosineHeadFn.apply(self.model(self.x), self.text_features, self.scale)
 
-    def __call__(self, images, labels, row_weight):
+    def __call__(self, images, labels, row_weight, soft_row=None):
         if engine.is_per_image_prefix(self.model.prefix):
+            self._soft_row = soft_row
             loss, self.logits = self.eager(images, labels, row_weight)
             return loss
-        return super().__call__(images, labels, row_weight)
+        return super().__call__(images, labels, row_weight, soft_row)
 
     def eager(self, images, labels, row_weight):
-        return vpt_step(self.model, self.text_features, self.scale, images, labels, row_weight, self.optimizer, return_logits=True)
+        return vpt_step(self.model, self.text_features, self.scale, images, labels, row_weight, self.optimizer, return_logits=True, soft=self.soft,
+                        soft_row=self._soft_row)
 
 
 class GraphedUptStep(GraphedStep):
     """upt_step (multimodal prompt: mixer + both towers forward and backward, towers on two streams) replayed from a HIP graph.  Every trainable
     parameter is captured, vpt_embeddings_deep included: with mix_deep (deep UPT) the graph holds the deep mixer and the tower's deep prompts."""
 
-    def __init__(self, model, logit_scale, optimizer):
-        super().__init__(optimizer)
+    def __init__(self, model, logit_scale, optimizer, soft=None):
+        super().__init__(optimizer, soft)
         self.model, self.scale = model, float(logit_scale)
 
     def params(self):
@@ -359,12 +415,12 @@ class GraphedUptStep(GraphedStep):
         return CosineHeadFn.apply(image_features, text_features, self.scale)
 
     def eager(self, images, labels, row_weight):
-        return upt_step(self.model, self.scale, images, labels, row_weight, self.optimizer, return_logits=True)
+        return upt_step(self.model, self.scale, images, labels, row_weight, self.optimizer, return_logits=True, soft=self.soft, soft_row=self._soft_row)
 
 
 def tip_step(model, image_features, clip_logits, labels, row_weight, optimizer, return_logits=False):
     """Tip-Adapter-F step on a models.TipAdapterModel with train_keys: cache head over cached image features and the CLIP logits of the trained
-    prompt (both constants of the step) -> weighted CE -> the keys' gradient -> optimizer.  No tower runs."""
+    prompt (both constants of the step) -> weighted CE -> the keys' gradient -> optimizer.  No tower runs.  Hard labels only (no soft targets)."""
     logits = model(image_features, clip_logits)
     loss = WeightedCEFn.apply(logits, labels, row_weight)
     return _finish(loss, [model.keys], optimizer, logits if return_logits else None)
@@ -402,7 +458,8 @@ class GraphedTipStep(GraphedStep):
 
 def adapter_step(model, image_features, text_features, scale, labels, row_weight, optimizer, return_logits=False):
     """CLIP-Adapter step on a models.ClipAdapterModel: feature adapter over cached image features -> cosine head against the fixed text features of
-    the trained prompt (constants of the step) -> weighted CE -> the gradients of w1 and w2 -> optimizer.  No tower runs."""
+    the trained prompt (constants of the step) -> weighted CE -> the gradients of w1 and w2 -> optimizer.  No tower runs.  Hard labels only (no soft
+    targets)."""
     feats = model(image_features)
     logits = CosineHeadFn.apply(feats, text_features, scale)
     loss = WeightedCEFn.apply(logits, labels, row_weight)

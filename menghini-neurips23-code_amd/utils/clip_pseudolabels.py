@@ -107,7 +107,9 @@ def pseudolabel_top_k(config, data_name, k, template, dataset, classnames, trans
     # a propagated list ("lp_"), a GMM list ("gmm_"), a balanced one ("ot_", "ot_lp_", "ot_gmm_") and a reference-style one never share a cache file
     lp = pl.propagation().infix if pl.propagation() is not None else ""
     filename = f"pseudolabels/{data_name}_{vis_encoder.replace('/', '')}_{config.LEARNING_PARADIGM}_{config.MODEL}_{k}_pseudolabels_{lp}split_{split_seed}.pickle"
-    if os.path.exists(filename):
+    # while a SoftTargetStore is installed (pl.soft_targets) an existing file is not read: a loaded list has no matrix behind it -- the pass runs and
+    # rewrites the same file (same name, same schema)
+    if os.path.exists(filename) and pl.soft_target_store() is None:
         with open(filename, "rb") as f:
             pseudolabels = pickle.load(f)
         dataset.filepaths = pseudolabels["filepaths"]
