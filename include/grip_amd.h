@@ -412,6 +412,50 @@ int grip_gmm_estep(const float* feats, const float* mean, const float* var, cons
                    void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 9 additions) Gaussian discriminant head (models/gda_models.py GdaHeadModel; csrc/gda_head.hip), after "A Hard-to-Beat Baseline for
+ * Training-free CLIP-based Adaptation" (Wang et al., ICLR 2024): class means and ONE shared full covariance of the unit image embeddings give the
+ * linear classifier  w_c = A^-1 mu_c,  bias_c = 1/2 mu_c . w_c - log pi_c,  A = S / W + rho (tr(S) / (W e)) I,  added to the CLIP logits.  The model is
+ * the one written here, NOT that paper's code: a ridge replaces its empirical-Bayes covariance estimate, rows may carry weights, the prior is the
+ * caller's, a class without rows contributes nothing.  All tensors f32 / int32 on the device; no atomics; no library math.
+ *
+ * grip_class_scatter: scatter_out [e, e] = S = sum_i r_i (feats_i - mean[y_i]) (feats_i - mean[y_i])^T   (the direct form; r = row_weight, NULL = 1)
+ *   feats [n, e], labels [n] int32, mean [c, e] (grip_gmm_mstep's, on Z_ic = r_i [y_i = c]).  A row whose label is outside 0 .. c - 1 or whose weight is 0
+ *   contributes nothing and its feature row is not read.  d = fl(feats - mean) is rounded once in the load path and the products r d_a d_b run on
+ *   the f32 MFMA.  The rows are reduced over a FIXED partition (chunks of 256 rows, grouped into at most 16 contiguous slices of
+ *   ceil(chunks / 16) chunks; a slice is one chain over its rows in ascending order, the slices are added in ascending order): the summation order
+ *   is a function of (n, e) alone, two calls are bit-equal, and the workspace is at most 16 e^2 floats whatever n is.  Only the lower triangle is
+ *   computed and then mirrored: scatter_out is bit-symmetric.  e a multiple of 4 up to 1024, n, c >= 1; feats and mean 16-byte aligned;
+ *   scatter_out must not alias an input.
+ *
+ * grip_spd_solve: M = a_scale a + ridge_rel a_scale (tr(a) / e) I,  M = L L^T,  M x_c = rhs_c for the c rows of rhs.
+ *   a [e, e] is read as symmetric from its LOWER triangle only (the upper one may hold anything); rhs, x_out [c, e]; factor_out [e, e] or NULL: L, zeros
+ *   above the diagonal; info_out: one device int32.  The trace is added in a fixed order on the device; M_ii = fmaf(a_scale, a_ii, shift) with
+ *   shift = ((ridge_rel a_scale) tr) / e, M_ij = a_scale a_ij.  Blocked right-looking Cholesky in f32 (panels of 64 columns, the last one ragged, one
+ *   launch per panel, no workgroup ever waits for another), the right-hand sides riding along as extra rows, then one back substitution per class;
+ *   true divisions and square roots.  info_out = 0, or j + 1 for the first pivot j that is not > 0: x_out and factor_out are then unspecified, but the
+ *   call returns and reads nothing out of bounds.  Bit-identical from call to call.  e a multiple of 4 up to 1024, c >= 1, a_scale > 0,
+ *   ridge_rel >= 0; x_out may be rhs; x_out must not alias a, factor_out no other operand.
+ *
+ * grip_linear_head: logits_out[i, c] = base_logits[i, c] + alpha ((img_emb_i . w_c) rn_i - bias_c),   rn_i = 1 / sqrt(sum_d img_emb_id^2)
+ *   img_emb [n, e] NOT normalised (as grip_cache_head_forward takes them, and with its rule: the reciprocal norm scales the SCORE, img_emb is never
+ *   copied; a zero row has rn = inf and 0 * inf = NaN in every column -- rows of non-zero norm are the caller's duty); w [c, e], bias [c];
+ *   base_logits [n, c] or NULL (0); logits_out may BE base_logits (in place).  argmax_out [n] int32 or NULL: the first index of the row's maximum
+ *   (0 for a row of NaNs).  One launch on the f32 MFMA: a score is one chain over e in ascending order, the row's sum of squares is accumulated on
+ *   chip in a fixed order, the [n, c] product never reaches memory on its own.  A row's bits depend on that row, w and bias alone -- not on n, on
+ *   its place in a tile or on the call -- and bit-equal classes score bit-equally.  e a multiple of 4 up to 1024, n, c >= 1, alpha finite; img_emb
+ *   and w 16-byte aligned.
+ * Every call refuses out-of-range arguments with nothing written; the workspace calls need no device. */
+int grip_class_scatter_workspace(int n, int c, int e, size_t* bytes);
+int grip_class_scatter(const float* feats, const int32_t* labels, const float* row_weight, const float* mean, int n, int c, int e, float* scatter_out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int grip_spd_solve_workspace(int e, int c, size_t* bytes);
+int grip_spd_solve(const float* a, float a_scale, float ridge_rel, const float* rhs, int e, int c, float* x_out, float* factor_out, int32_t* info_out,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int grip_linear_head_workspace(int n, int c, int e, size_t* bytes);
+int grip_linear_head(const float* img_emb, const float* w, const float* bias, float alpha, const float* base_logits, int n, int c, int e,
+                     float* logits_out, int32_t* argmax_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * (ABI 9 additions) Balanced pseudolabel assignment over a pool (pseudolabels.BalancedAssignment; csrc/sinkhorn.hip): the [n, c] probabilities are
  * treated as an optimal-transport problem -- rows sum to one, columns to n x a class prior -- and Sinkhorn-Knopp iterated on it (Cuturi 2013; SeLa,
  * Asano et al. 2020; SwAV, Caron et al. 2020).  The row scaling is the softmax normaliser, so the only state between iterations is b [c]:

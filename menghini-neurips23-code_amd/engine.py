@@ -1041,6 +1041,86 @@ def gmm_transduce(feats, probs, idx, sim, lam=1.0, iters=10, z_iters=5, var_floo
     return z, pred, mean, var, count
 
 
+GDA_SCATTER_ROWS = 256      # csrc/gda_head.hip: GD_ROWS, the fixed row chunk of the scatter
+GDA_SCATTER_SLICES = 16     # csrc/gda_head.hip: GD_SLICES, the K-slices the chunks are grouped into at most
+GDA_MAX_E = 1024            # csrc/gda_head.hip: GD_MAX_E
+
+
+def _gda_workspace(query, dims, device):
+    nbytes = c_size_t()
+    native.check(query(*dims, byref(nbytes)))
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+
+def class_scatter(feats, labels, row_weight, mean):
+    """S f32 [e, e] = sum_i r_i (feats_i - mean[labels_i]) (feats_i - mean[labels_i])^T, the within-class scatter in its direct form on the native
+    SYRK (csrc/gda_head.hip): feats [n, e] taken as given, labels int32 [n], row_weight f32 [n] or None (1), mean [c, e].  No atomics, a fixed row
+    partition, bit-symmetric and bit-identical from call to call.  A row with a label outside 0 .. c - 1 or a weight of 0 contributes nothing (the
+    values of labels are the caller's: models.gda_models.GdaHeadModel validates them on the host)."""
+    if not torch.is_tensor(feats) or feats.dim() != 2 or not torch.is_tensor(mean) or mean.dim() != 2 or mean.shape[1] != feats.shape[1]:
+        raise native.GripError(f"class_scatter: feats [n, e] and mean [c, e] expected, got {getattr(feats, 'shape', type(feats))} and "
+                               f"{getattr(mean, 'shape', type(mean))}")
+    (n, e), c = feats.shape, mean.shape[0]
+    f = _gmm_operand("class_scatter", "feats", feats, (n, e))
+    y = _gmm_operand("class_scatter", "labels", labels, (n,), f, torch.int32)
+    r = None if row_weight is None else _gmm_operand("class_scatter", "row_weight", row_weight, (n,), f)
+    mu = _gmm_operand("class_scatter", "mean", mean, (c, e), f)
+    require_gpu(f.device)
+    lib = native.lib()
+    ws = _gda_workspace(lib.grip_class_scatter_workspace, (n, c, e), f.device)
+    out = torch.empty(e, e, dtype=torch.float32, device=f.device)
+    native.check(lib.grip_class_scatter(_ptr(f), _ptr(y), _ptr(r), _ptr(mu), n, c, e, _ptr(out), _ptr(ws), ws.numel(), _stream()))
+    return out
+
+
+def spd_solve(a, rhs, a_scale=1.0, ridge_rel=0.0, want_factor=False):
+    """x f32 [c, e] with M x_c = rhs_c, M = a_scale a + ridge_rel a_scale (tr(a) / e) I, by the native blocked Cholesky (csrc/gda_head.hip); a [e, e] is
+    read from its lower triangle only.  want_factor: (x, L) with M = L L^T, L lower triangular.  Reads the kernel's info word (one synchronisation) and
+    raises GripError naming the pivot when M is not positive definite in f32."""
+    if not torch.is_tensor(a) or a.dim() != 2 or a.shape[0] != a.shape[1] or not torch.is_tensor(rhs) or rhs.dim() != 2 or rhs.shape[1] != a.shape[0]:
+        raise native.GripError(f"spd_solve: a [e, e] and rhs [c, e] expected, got {getattr(a, 'shape', type(a))} and {getattr(rhs, 'shape', type(rhs))}")
+    e, c = a.shape[0], rhs.shape[0]
+    aa = _gmm_operand("spd_solve", "a", a, (e, e))
+    b = _gmm_operand("spd_solve", "rhs", rhs, (c, e), aa)
+    require_gpu(aa.device)
+    lib = native.lib()
+    ws = _gda_workspace(lib.grip_spd_solve_workspace, (e, c), aa.device)
+    x = torch.empty(c, e, dtype=torch.float32, device=aa.device)
+    fac = torch.empty(e, e, dtype=torch.float32, device=aa.device) if want_factor else None
+    info = torch.empty(1, dtype=torch.int32, device=aa.device)
+    native.check(lib.grip_spd_solve(_ptr(aa), float(a_scale), float(ridge_rel), _ptr(b), e, c, _ptr(x), _ptr(fac), _ptr(info), _ptr(ws), ws.numel(),
+                                    _stream()))
+    bad = int(info.item())
+    if bad:
+        raise native.GripError(f"spd_solve: the matrix is not positive definite in f32: pivot {bad - 1} of {e} is not > 0 "
+                               f"(a_scale = {float(a_scale):g}, ridge_rel = {float(ridge_rel):g})")
+    return (x, fac) if want_factor else x
+
+
+def linear_head(img_emb, w, bias, alpha, base_logits=None, want_argmax=False):
+    """logits f32 [n, c] = base_logits + alpha * ((img_emb @ w.T) / |img_emb| - bias) in ONE launch of the native head (csrc/gda_head.hip), no autograd;
+    img_emb [n, e] NOT normalised, w [c, e], bias [c], base_logits [n, c] or None (0).  The result is a new tensor (the C entry point also works in
+    place).  want_argmax: (logits, pred int32 [n]), the first arg-max of every row."""
+    if not torch.is_tensor(img_emb) or img_emb.dim() != 2 or not torch.is_tensor(w) or w.dim() != 2 or w.shape[1] != img_emb.shape[1]:
+        raise native.GripError(f"linear_head: img_emb [n, e] and w [c, e] expected, got {getattr(img_emb, 'shape', type(img_emb))} and "
+                               f"{getattr(w, 'shape', type(w))}")
+    (n, e), c = img_emb.shape, w.shape[0]
+    f = _gmm_operand("linear_head", "img_emb", img_emb, (n, e))
+    ww = _gmm_operand("linear_head", "w", w, (c, e), f)
+    b = _gmm_operand("linear_head", "bias", bias, (c,), f)
+    if base_logits is None:
+        out, base = torch.empty(n, c, dtype=torch.float32, device=f.device), None
+    else:
+        out = _gmm_operand("linear_head", "base_logits", base_logits, (n, c), f).clone(memory_format=torch.contiguous_format)
+        base = out
+    require_gpu(f.device)
+    lib = native.lib()
+    ws = _gda_workspace(lib.grip_linear_head_workspace, (n, c, e), f.device)
+    pred = torch.empty(n, dtype=torch.int32, device=f.device) if want_argmax else None
+    native.check(lib.grip_linear_head(_ptr(f), _ptr(ww), _ptr(b), float(alpha), _ptr(base), n, c, e, _ptr(out), _ptr(pred), _ptr(ws), ws.numel(), _stream()))
+    return (out, pred) if want_argmax else out
+
+
 SINKHORN_ROWS = 16      # csrc/sinkhorn.hip: SK_ROWS, the fixed row partition of the column sums
 
 

@@ -19,7 +19,7 @@ import torch
 
 from .. import clip, dist as gdist, pseudolabels as pl, steps
 from ..engine import cosine_head
-from ..models import ClipAdapterModel, CustomImageEncoder, CustomTextEncoder, ImagePrefixModel, MaPLeModel, TextPrefixModel, TipAdapterModel, UPTModel
+from ..models import ClipAdapterModel, CustomImageEncoder, CustomTextEncoder, GdaHeadModel, ImagePrefixModel, MaPLeModel, TextPrefixModel, TipAdapterModel, UPTModel
 from ..utils import pseudolabel_top_k
 
 log = logging.getLogger(__name__)
@@ -68,6 +68,12 @@ class TrainingStrategy:
         if bool(getattr(config, "CLIP_ADAPTER", False)) and self.modality != "text":
             log.info(f"CLIP_ADAPTER is ignored by the {self.modality} strategies: their image features move with the prompt (textual strategies only)")
         self.clip_adapter()      # (raises when CLIP_ADAPTER and TIP_ADAPTER are both set)
+        # GDA_HEAD (textual strategies): the Gaussian discriminant head fitted to the cached training features after each prompt training
+        # (build_gda_head); None = off
+        self.gda, self.gda_classes, self.gda_search = None, None, None
+        if bool(getattr(config, "GDA_HEAD", False)) and self.modality != "text":
+            log.info(f"GDA_HEAD is ignored by the {self.modality} strategies: their image features move with the prompt (textual strategies only)")
+        self.gda_head()          # (raises when GDA_HEAD is set together with TIP_ADAPTER or CLIP_ADAPTER)
         # LABEL_PROPAGATION (all modalities, default False): every pseudolabel pass propagates the head's probabilities over the pool's kNN graph
         # (LP_K 16, LP_ALPHA 0.8, LP_GAMMA 10, LP_ITERS 10: untuned).  Textual strategies keep the graph per pool -- their image tower is frozen, the graph
         # is an invariant of the run; visual and multimodal strategies rebuild it every pass: their features move with the prompt.
@@ -206,10 +212,21 @@ class TrainingStrategy:
             raise ValueError("CLIP_ADAPTER and TIP_ADAPTER are two different heads on the same image features: set one of them")
         return on
 
+    def gda_head(self):
+        """Gaussian discriminant head for the textual strategies: config GDA_HEAD, default False (GDA_ALPHA 1.0, GDA_SHRINK 1.0, GDA_PSEUDO_WEIGHT 1.0,
+        GDA_SEARCH False, GDA_ALPHA_GRID (0.1, 0.3, 1, 3, 10): untuned).  Their image tower is frozen and their training features are cached, so the
+        head costs no tower pass and no training.  Visual and multimodal strategies ignore it, as they ignore TIP_ADAPTER.  Together with
+        TIP_ADAPTER or CLIP_ADAPTER it is refused: they are different heads on the same features, and stacking them is not defined here."""
+        on = self.modality == "text" and bool(getattr(self.config, "GDA_HEAD", False))
+        if on and (bool(getattr(self.config, "TIP_ADAPTER", False)) or bool(getattr(self.config, "CLIP_ADAPTER", False))):
+            raise ValueError("GDA_HEAD, TIP_ADAPTER and CLIP_ADAPTER are different heads on the same image features: set one of them")
+        return on
+
     def define_model(self, classes=None):
         c, dev = self.config, self.device
         self.tip = None      # a cache belongs to the prompt it was built after: validation during the next training sees CLIP logits alone
         self.adapter = None  # and so does a feature adapter
+        self.gda = None      # and a discriminant head
         classes = classes if classes is not None else self.classes
         if self.modality == "text":
             deep = getattr(self, "initial_deep_prefix", None)
@@ -523,6 +540,8 @@ class TrainingStrategy:
             logits, _, am, _ = cosine_head(image_features, text_features, self.scale(), want_probs=False)
             if self.tip is not None:      # TIP_ADAPTER: the cache term of the iteration's training set
                 logits = self._add_cache_term(image_features, logits, classes)
+            if self.gda is not None:      # GDA_HEAD: the discriminant term of the iteration's training set
+                logits = self._add_gda_term(image_features, logits, classes)
             outs.append(logits)
         logits = torch.cat(outs) if outs else torch.empty(0, len(classes), device=self.device)
         logits = gdist.gather_in_dataset_order(logits, len(data), int(self.config.BATCH_SIZE))
@@ -549,6 +568,8 @@ class TrainingStrategy:
             self.build_tip_cache(train_data, val_data, only_seen=only_seen)
         if self.clip_adapter():
             self.build_feature_adapter(train_data, val_data, only_seen=only_seen)
+        if self.gda_head():
+            self.build_gda_head(train_data, val_data, only_seen=only_seen)
         return best_acc, best_prompt
 
     # ------------------------------------------------------------------ Tip-Adapter cache (TIP_ADAPTER, textual strategies)
@@ -680,6 +701,51 @@ class TrainingStrategy:
         self.adapter = ClipAdapterModel.load(path, device=self.device)
         return self.adapter
 
+    # ------------------------------------------------------------------ Gaussian discriminant head (GDA_HEAD, textual strategies)
+    def build_gda_head(self, train_data, val_data=None, only_seen=False):
+        """The discriminant head of the iteration just trained: models.GdaHeadModel.fit on the training set's cached frozen features (labelled shots
+        and pseudolabelled pool rows: the rows the prompt steps read; a pseudolabelled row weighs GDA_PSEUDO_WEIGHT), ridge GDA_SHRINK, no training.
+        GDA_SEARCH picks alpha from GDA_ALPHA_GRID on the validation set.  From here on predict() -- hence _run_validation, test_predictions and
+        evaluation -- adds alpha * (normalize(f) . w_c - bias_c) to the logits it computes.
+
+        The pseudolabel pass is NOT touched: assign_pseudo_labels and the frozen-CLIP pass keep ranking the pool by the CLIP logits of the prompts
+        alone, so pseudolabel lists and prompt files are the same with the switch on or off."""
+        c = self.config
+        classes, ids, lut = self._class_space(only_seen)
+        with torch.random.fork_rng(devices=[]):      # (_tip_inputs' DataLoader draws its base seed from the global stream: see build_feature_adapter)
+            feats, _, labs, names = self._tip_inputs(train_data, classes, lut)
+        pseudo = [getattr(self, "fpl", False) and (self.paradigm == "ul" or n in self.check_unlabeled) for n in names]
+        self.gda = GdaHeadModel.fit(feats, labs, pseudo, len(classes), pseudo_weight=float(getattr(c, "GDA_PSEUDO_WEIGHT", 1.0)),
+                                    shrink=float(getattr(c, "GDA_SHRINK", 1.0)), alpha=float(getattr(c, "GDA_ALPHA", 1.0)))
+        self.gda_classes, self.gda_search = list(classes), None
+        if bool(getattr(c, "GDA_SEARCH", False)) and val_data is not None and len(val_data):
+            with torch.random.fork_rng(devices=[]):
+                vf, vl, vy, _ = self._tip_inputs(val_data, classes, lut)
+            if len(vy):
+                self.gda_search = self.gda.search(list(getattr(c, "GDA_ALPHA_GRID", (0.1, 0.3, 1.0, 3.0, 10.0))), vf, vl, vy)
+                log.info(f"GDA head search: alpha {self.gda_search[0]:g} (validation accuracy {self.gda_search[1]:.3f})")
+        return self.gda
+
+    def load_gda_head(self, path, classes=None):
+        """Install a head file written by utils.save_parameters(..., gda=strategy.gda); `classes`: its class list (default: all classes)."""
+        self.gda = GdaHeadModel.load(path, device=self.device)
+        self.gda_classes = list(classes if classes is not None else self.classes)
+        return self.gda
+
+    @torch.no_grad()
+    def _add_gda_term(self, image_features, logits, classes):
+        """logits [N, len(classes)] + the discriminant term of the columns the head knows (all of them when `classes` is the head's own list: one
+        launch; otherwise the term is computed against no base and its columns are gathered), as _add_cache_term does for the Tip cache."""
+        if list(classes) == self.gda_classes:
+            return self.gda(image_features, logits)
+        term = self.gda(image_features, torch.zeros(logits.shape[0], len(self.gda_classes), device=logits.device))
+        pos = {c: i for i, c in enumerate(self.gda_classes)}
+        cols = [(j, pos[c]) for j, c in enumerate(classes) if c in pos]
+        if cols:
+            dst, src = (torch.tensor(x, device=logits.device) for x in zip(*cols))
+            logits[:, dst] += term[:, src]
+        return logits
+
     # ------------------------------------------------------------------ evaluation
     def test_predictions(self, data, standard_zsl=False):
         import pandas as pd
@@ -806,7 +872,7 @@ class TrainingStrategy:
             out = self.train(data, val_data, only_seen=only_seen, iter_train=True)
             from ..utils import save_parameters, save_pseudo_labels
             save_pseudo_labels(list(data.filepaths), list(data.labels), c, niter)     # compute_metrics.py:150-154
-            save_parameters(out[1], c, iteration=niter, cache=self.tip, adapter=self.adapter)
+            save_parameters(out[1], c, iteration=niter, cache=self.tip, adapter=self.adapter, gda=self.gda)
             log.info(f"GRIP iteration {niter}/{num_iter}: {c.N_PSEUDOSHOTS} pseudo-shots per class, val acc {out[0]:.3f}")
         return out
 

@@ -106,6 +106,13 @@ _SIGS = {
     "grip_gmm_estep_workspace": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
     "grip_gmm_estep": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                c_void_p, c_void_p, c_size_t, c_void_p]),
+    # (ABI 9 additions) Gaussian discriminant head: within-class scatter (SYRK), SPD solve (blocked Cholesky), pool-sized linear head (csrc/gda_head.hip)
+    "grip_class_scatter_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "grip_class_scatter": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "grip_spd_solve_workspace": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "grip_spd_solve": (c_int, [c_void_p, c_float, c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "grip_linear_head_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "grip_linear_head": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     # (ABI 9 additions) balanced (Sinkhorn-Knopp) assignment of a pool's probabilities to a class prior (csrc/sinkhorn.hip)
     "grip_sinkhorn_workspace": (c_int, [c_int, c_int, POINTER(c_size_t)]),
     "grip_sinkhorn_balance": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,

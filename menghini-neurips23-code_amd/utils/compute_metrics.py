@@ -67,7 +67,12 @@ def adapter_path(config, iteration=None):
     return _prompt_base(config, iteration) + "_adapter.pickle"
 
 
-def save_parameters(obj, config, iteration=None, cache=None, adapter=None):
+def gda_head_path(config, iteration=None):
+    """The Gaussian discriminant head file of a run (GDA_HEAD), beside its prompt file."""
+    return _prompt_base(config, iteration) + "_gda.pickle"
+
+
+def save_parameters(obj, config, iteration=None, cache=None, adapter=None, gda=None):
     """utils/compute_metrics.py:105-147 of the reference.  Textual / visual prompts: `obj` (a list holding the prompt as a
     numpy array) pickled to `{base}.pickle`.  MODALITY == "multi": `obj` is the positional list of the eight trainable pieces
     (UPT_NAMES order, methods/*/multimodal_prompt.py:149-158) and each goes to its own file -- the five state_dicts with
@@ -75,13 +80,16 @@ def save_parameters(obj, config, iteration=None, cache=None, adapter=None):
     MaPLeModel and `obj` (ctx, compound_prompts_text, proj_weight, proj_bias) is one pickle, `{base}_maple.pickle`.  Returns the file(s) written.
     `cache` (a models.TipAdapterModel, the strategy's `tip`; TIP_ADAPTER) goes to a file of its own, `{base}_tip.pickle` (tip_cache_path): keys, class
     ids, key weights and hyperparameters -- the prompt file and the return value are what they are without it.  `adapter` (a
-    models.ClipAdapterModel, the strategy's `adapter`; CLIP_ADAPTER) likewise goes to `{base}_adapter.pickle` (adapter_path): w1, w2, ratio."""
+    models.ClipAdapterModel, the strategy's `adapter`; CLIP_ADAPTER) likewise goes to `{base}_adapter.pickle` (adapter_path): w1, w2, ratio; `gda` (a
+    models.GdaHeadModel, the strategy's `gda`; GDA_HEAD) to `{base}_gda.pickle` (gda_head_path): mean, w, bias, alpha."""
     os.makedirs("trained_prompts", exist_ok=True)
     base = _prompt_base(config, iteration)
     if cache is not None:
         cache.save(base + "_tip.pickle")
     if adapter is not None:
         adapter.save(base + "_adapter.pickle")
+    if gda is not None:
+        gda.save(base + "_gda.pickle")
     if getattr(config, "MODALITY", None) == "multi" and getattr(config, "MAPLE", False):
         # MaPLe: [ctx, compound_prompts_text, proj_weight, proj_bias] as numpy (TrainingStrategy.prompt_snapshot), one pickle
         with open(base + "_maple.pickle", "wb") as f:
