@@ -63,6 +63,16 @@ int grip_debug_split_rows(const float* x, void* out, int64_t rows, int K, void* 
 /* 1 when the last split-f16 GEMM launch formed the a_hi w_lo product, 0 when it ran the two-pass kernel (every element of W an f16 number:
  * grip_debug_gemm_split checks W itself, a tower at grip_tower_finalize), -1 before any launch. */
 int grip_debug_split_last_wlo(void);
+/* One GEMM launch of the f32 tower (tier 1: A, W, resid and every output f32) or of the split-f16 tower (tier 2: A and W images in the split layout,
+ * bias / resid / out f32, the epi 2 output in the split layout; w_exact != 0: W is the duplicated image of f16-exact weights, the two-pass form) with every
+ * field of its argument block given (tests/test_gpu_tier_gemm_kernels.py): out / out2 / resid are [M, ldc] (out may point some columns into a wider row).
+ * Nothing is checked beyond what the launcher itself checks. */
+int grip_debug_gemm_tier(int tier, int w_exact, int epi, const void* A, const void* W, int M, int N, int K, int ldc, const float* bias, const void* resid,
+                         void* out, void* out2, float scalar, int64_t m_pad, void* stream);
+/* The weight image of the split-f16 tier: W [rows, K] f32 -> image (4 bytes per element) in the split layout, scaled as the tier's kernels expect; dup != 0:
+ * then rewritten in place as the duplicated image [32 hi | 32 hi].  flags_out[0] = 1 when a scaled element left the finite f16 range, flags_out[1] = 1 when an
+ * element is not an f16 number (else 0). */
+int grip_debug_split_weights(const float* W, void* image, int64_t rows, int K, int dup, int* flags_out, void* stream);
 /* Attention of a precision-2 tower: qkv [B*S, 3*H*64] f32 -> out [B*S, H*64] in the split layout (4 bytes per element).  mfma != 0: the matrix-pipe
  * kernel (csrc/attention_split.hip, S <= 320), else the f32 vector-ALU kernel writing the split layout (any S). */
 int grip_debug_attention_split(const void* qkv, void* out, int B, int S, int H, int causal, int mfma, void* stream);

@@ -871,6 +871,30 @@ extern "C" int grip_debug_split_last_wlo(void) { return gemm_split_last_wlo(); }
 extern "C" int grip_debug_split_rows(const float* x, void* out, int64_t rows, int K, void* stream) {
     return launch_split_rows(x, out, rows, K, K, (hipStream_t)stream);
 }
+// One GEMM launch of the f32 (tier 1) or split-f16 (tier 2) tower with every field its launcher reads as given (tests/test_gpu_tier_gemm_kernels.py):
+// ldc != N and the two-pass form on any shape.  No logic of its own: what launch_gemm refuses is refused.
+extern "C" int grip_debug_gemm_tier(int tier, int w_exact, int epi, const void* A, const void* W, int M, int N, int K, int ldc, const float* bias, const void* resid,
+                                    void* out, void* out2, float scalar, int64_t m_pad, void* stream) {
+    GemmArgs a{};
+    a.f32 = tier; a.w_exact = w_exact;
+    a.A = A; a.W = W; a.M = M; a.N = N; a.K = K; a.ldc = ldc; a.m_pad = m_pad; a.bias = bias; a.resid = resid; a.out = out; a.out2 = out2; a.scalar = scalar;
+    return launch_gemm(epi, a, (hipStream_t)stream);
+}
+// Weight image of the split-f16 tier as grip_tower_finalize builds it: W [rows, K] f32 -> the split layout (x SP1_W_SCALE), with dup != 0 then rewritten in
+// place as the duplicated image; flags_out[0] = overflow, flags_out[1] = some element is no f16 number.
+extern "C" int grip_debug_split_weights(const float* W, void* image, int64_t rows, int K, int dup, int* flags_out, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    int* flag = nullptr;
+    GRIP_CHECK_HIP(hipMalloc((void**)&flag, 2 * sizeof(int)));
+    int rc = hipMemsetAsync(flag, 0, 2 * sizeof(int), s) == hipSuccess ? launch_split_rows(W, image, rows, K, K, s, 1, flag, flag + 1) : GRIP_ERR_HIP;
+    if (!rc && dup) rc = launch_split_dup_weights(image, image, rows, K, s);
+    if (!rc && (hipMemcpyAsync(flags_out, flag, 2 * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)) {
+        grip_set_error("debug_split_weights: HIP error");
+        rc = GRIP_ERR_HIP;
+    }
+    (void)hipFree(flag);
+    return rc;
+}
 // Attention of a precision-2 tower: qkv f32 -> out in the split layout (4 bytes per element); mfma != 0: attention_split.hip (S <= 320), else the
 // f32 vector-ALU kernel with split output
 extern "C" int grip_debug_attention_split(const void* qkv, void* out, int B, int S, int H, int causal, int mfma, void* stream) {
