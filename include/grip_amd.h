@@ -456,6 +456,50 @@ int grip_linear_head(const float* img_emb, const float* w, const float* bias, fl
                      float* logits_out, int32_t* argmax_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 9 additions) Trained linear probe (models/probe_models.py LinearProbeModel; csrc/linear_probe.hip): the linear classifier on frozen features
+ * that the CLIP and CoOp papers compare against, in the text-initialised form of LP++ -- a residual on the CLIP logits that starts at zero.  The model is
+ * the one written here, NOT those papers' code.  All tensors f32 / int32 on the device; no atomics; every sum in a fixed order.
+ *   x_ic   = base_ic + scale (feats_i . w_c) + b_c                 feats [n, e] taken as given (unit rows are the caller's duty), base [n, c] or NULL (0)
+ *   t_i    = onehot(labels_i) for 0 <= labels_i < c;  soft_i (non-negative, [n, c]) for labels_i == -1 when soft is given
+ *   T_i    = sum_c t_ic (ascending c)
+ *   loss   = norm sum_i r_i (T_i lse(x_i) - t_i . x_i)             r = row_weight, NULL = 1; norm = 1 / sum_i r_i is the CALLER's
+ *   g_ic   = r_i (T_i softmax(x_i)_c - t_ic),   grad_w = norm scale sum_i g_ic feats_i,   grad_b = norm sum_i g_ic
+ * A row whose label is neither in 0 .. c - 1 nor a usable -1, or whose weight is exactly 0, contributes nothing and its feature, base and soft rows are
+ * not read.  These are the DATA terms only: the ridge (l2 / 2) |w|^2 enters in grip_probe_fit's update.
+ *
+ * grip_probe_objective: loss_out [1], grad_w [c, e], grad_b [c] at (w [c, e], b [c] or NULL = zeros).  Three launches:
+ *   1. scores on the f32 MFMA (a score is one chain over e in ascending order), x = base + fmaf(scale, score, b), the row maximum, sum of
+ *      exp(x - max) and lse = max + logf(sum) on chip -- neither x nor softmax(x) is ever written to memory -- then g = r fmaf(T, exp(x - max) / sum, -t)
+ *      written ONCE to the workspace, and r fmaf(T, lse, -t . x) added over the 32 rows of a workgroup in ascending order;
+ *   2. the transposed contraction sum_i g_ic feats_id on the f32 MFMA over a FIXED row partition: chunks of 64 rows grouped into at most
+ *      cap = min(64, max(4, 1024 / (ceil(c / 128) ceil(e / 64)))) contiguous slices of ceil(chunks / cap) chunks; a slice is one chain over its rows in
+ *      ascending order (grad_b: the rows = fgrp mod 4 of a slice in four chains, then (l0 + l1) + (l2 + l3));
+ *   3. the slices in ascending order, then ONE product: grad_w = fl(norm scale) sum, grad_b = norm sum, loss = norm sum (the workgroups' losses as 256
+ *      strided sums, then those in ascending order).
+ *   The order is a function of (n, c, e) alone: two calls are bit-equal whatever ran beside them, and bit-equal classes (w_c, b_c, base column, targets)
+ *   get bit-equal grad_w rows and grad_b entries.  c <= 256 reads feats once for the scores (and once for the contraction); above that the row tile
+ *   is staged again for every 64 classes.
+ *
+ * grip_probe_fit: `iters` iterations of launches 1 and 2 and the update (3 launches each, no host synchronisation, no allocation, capturable in a
+ *   graph) -- full-batch heavy-ball descent with torch.optim.SGD(momentum) semantics, per element and in exactly this rounding sequence:
+ *       gw = fl(norm scale) sum_slices         G = fmaf(l2, w, gw)         mom_w = fmaf(momentum, mom_w, G)        w = fmaf(-lr, mom_w, w)
+ *       gb = norm sum_slices                                               mom_b = fmaf(momentum, mom_b, gb)       b = fmaf(-lr, mom_b, b)
+ *   (three fused multiply-adds for w, two for b; the only plain products are norm scale and its product with the sum).  w, b, mom_w, mom_b are in/out
+ *   and the caller's: fit(k1) followed by fit(k2) is bit-equal to fit(k1 + k2).  loss_trace [iters] or NULL: the data term at the START of each iteration.
+ *
+ * Limits: n >= 1, 1 <= c <= 1024, e a multiple of 4 up to 1024; feats and w 16-byte aligned; scale, norm, lr finite and > 0, l2 >= 0 finite,
+ * 0 <= momentum < 1, iters >= 1; no output may alias an input or another output.  The workspace holds g [n, c], the slice partials and the workgroups'
+ * losses.  Every call refuses out-of-range arguments with nothing written; the workspace calls need no device. */
+int grip_probe_objective_workspace(int n, int c, int e, size_t* bytes);
+int grip_probe_objective(const float* feats, const float* w, const float* b, const float* base, const int32_t* labels, const float* soft,
+                         const float* row_weight, float scale, float norm, int n, int c, int e, float* loss_out, float* grad_w, float* grad_b,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int grip_probe_fit_workspace(int n, int c, int e, size_t* bytes);
+int grip_probe_fit(const float* feats, const float* base, const int32_t* labels, const float* soft, const float* row_weight, float scale, float norm,
+                   float l2, float lr, float momentum, int iters, int n, int c, int e, float* w, float* b, float* mom_w, float* mom_b, float* loss_trace,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * (ABI 9 additions) Balanced pseudolabel assignment over a pool (pseudolabels.BalancedAssignment; csrc/sinkhorn.hip): the [n, c] probabilities are
  * treated as an optimal-transport problem -- rows sum to one, columns to n x a class prior -- and Sinkhorn-Knopp iterated on it (Cuturi 2013; SeLa,
  * Asano et al. 2020; SwAV, Caron et al. 2020).  The row scaling is the softmax normaliser, so the only state between iterations is b [c]:

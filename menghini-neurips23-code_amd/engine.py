@@ -1121,6 +1121,108 @@ def linear_head(img_emb, w, bias, alpha, base_logits=None, want_argmax=False):
     return (out, pred) if want_argmax else out
 
 
+PROBE_SCORE_ROWS = 32       # csrc/linear_probe.hip: PB_BM, the rows whose losses one workgroup of the score kernel adds
+PROBE_ROWS = 64             # csrc/linear_probe.hip: PB_ROWS, the fixed row chunk of the contraction
+PROBE_MAX_C = 1024          # csrc/linear_probe.hip: PB_MAX_C
+
+
+def probe_slice_cap(c, e):
+    """The most K-slices the contraction of grip_probe_objective cuts n rows into (csrc/linear_probe.hip, probe_plan): a function of (c, e) alone."""
+    return min(64, max(4, 1024 // (((c + 127) // 128) * ((e + 63) // 64))))
+
+
+def probe_slices(n, c, e):
+    """(chunks per slice, slices) of the contraction's fixed row partition."""
+    nch = (n + PROBE_ROWS - 1) // PROBE_ROWS
+    per = (nch + probe_slice_cap(c, e) - 1) // probe_slice_cap(c, e)
+    return per, (nch + per - 1) // per
+
+
+def _probe_operands(who, feats, base, labels, soft, row_weight, c):
+    if not torch.is_tensor(feats) or feats.dim() != 2:
+        raise native.GripError(f"{who}: feats [n, e] expected, got {getattr(feats, 'shape', type(feats))}")
+    n, e = feats.shape
+    f = _gmm_operand(who, "feats", feats, (n, e))
+    bs = None if base is None else _gmm_operand(who, "base", base, (n, c), f)
+    y = _gmm_operand(who, "labels", labels, (n,), f, torch.int32)
+    sf = None if soft is None else _gmm_operand(who, "soft", soft, (n, c), f)
+    r = None if row_weight is None else _gmm_operand(who, "row_weight", row_weight, (n,), f)
+    require_gpu(f.device)
+    return f, bs, y, sf, r, n, e
+
+
+def _probe_scalar(who, name, v, positive=True):
+    v = float(v)
+    if v != v or v in (float("inf"), float("-inf")) or (v <= 0 if positive else v < 0):
+        raise native.GripError(f"{who}: {name} = {v:g} (must be finite and {'> 0' if positive else '>= 0'})")
+    return v
+
+
+def probe_norm(labels, soft, row_weight, c):
+    """nu = 1 / sum_i r_i over the rows that contribute to grip_probe_objective (a label in 0 .. c - 1, or -1 with soft given; a weight that is not 0),
+    as a Python float: the sum runs on the device in float64, reading it back is ONE synchronisation."""
+    ok = ((labels >= 0) & (labels < c)) | ((labels == -1) if soft is not None else torch.zeros_like(labels, dtype=torch.bool))
+    r = torch.ones(labels.shape[0], dtype=torch.float64, device=labels.device) if row_weight is None else row_weight.double()
+    total = float(torch.where(ok & (r != 0), r, torch.zeros_like(r)).sum().item())
+    if not total > 0:
+        raise native.GripError(f"probe_norm: the weights of the contributing rows add up to {total:g} (no row contributes)")
+    return 1.0 / total
+
+
+def probe_objective(feats, w, b, base, labels, soft, row_weight, scale, norm):
+    """(loss 0-d, grad_w [c, e], grad_b [c]), the DATA term of the linear probe of include/grip_amd.h and its gradient on the native kernels
+    (csrc/linear_probe.hip): x = base + scale feats @ w.T + b, loss = norm sum_i r_i (T_i lse(x_i) - t_i . x_i) with t = onehot(labels) or, for labels == -1,
+    the row of soft.  feats [n, e] taken as given; b, base, soft, row_weight may be None.  Three launches, no atomics, bit-identical from call to call."""
+    if not torch.is_tensor(w) or w.dim() != 2:
+        raise native.GripError(f"probe_objective: w [c, e] expected, got {getattr(w, 'shape', type(w))}")
+    c = w.shape[0]
+    f, bs, y, sf, r, n, e = _probe_operands("probe_objective", feats, base, labels, soft, row_weight, c)
+    ww = _gmm_operand("probe_objective", "w", w, (c, e), f)
+    bb = None if b is None else _gmm_operand("probe_objective", "b", b, (c,), f)
+    scale, norm = _probe_scalar("probe_objective", "scale", scale), _probe_scalar("probe_objective", "norm", norm)
+    lib = native.lib()
+    ws = _gda_workspace(lib.grip_probe_objective_workspace, (n, c, e), f.device)
+    loss = torch.empty(1, dtype=torch.float32, device=f.device)
+    gw = torch.empty(c, e, dtype=torch.float32, device=f.device)
+    gb = torch.empty(c, dtype=torch.float32, device=f.device)
+    native.check(lib.grip_probe_objective(_ptr(f), _ptr(ww), _ptr(bb), _ptr(bs), _ptr(y), _ptr(sf), _ptr(r), scale, norm, n, c, e, _ptr(loss), _ptr(gw),
+                                          _ptr(gb), _ptr(ws), ws.numel(), _stream()))
+    return loss[0], gw, gb
+
+
+def probe_fit(feats, base, labels, soft, row_weight, scale, l2, lr, momentum, iters, w, b, state=None, want_trace=False, norm=None):
+    """(w, b, state[, trace]): `iters` full-batch heavy-ball iterations of the linear probe (grip_probe_fit: torch.optim.SGD(momentum) semantics on
+    norm sum_i r_i CE_i + (l2 / 2) |w|^2, three launches an iteration, no host synchronisation, capturable in a graph).  w [c, e] and b [c] are the start
+    and are NOT modified: the result is new tensors.  state = (mom_w, mom_b, norm, workspace) as an earlier call returned it (None: zero momentum):
+    probe_fit(k1) and then probe_fit(k2, state=...) give the bits of probe_fit(k1 + k2).  norm = 1 / sum of the contributing rows' weights comes from
+    `norm`, else from `state`, else from probe_norm -- the only synchronisation, and only when the caller gave neither.  trace f32 [iters]: the data
+    term at the start of every iteration (stays on the device)."""
+    if not torch.is_tensor(w) or w.dim() != 2:
+        raise native.GripError(f"probe_fit: w [c, e] expected, got {getattr(w, 'shape', type(w))}")
+    c = w.shape[0]
+    f, bs, y, sf, r, n, e = _probe_operands("probe_fit", feats, base, labels, soft, row_weight, c)
+    ww = _gmm_operand("probe_fit", "w", w, (c, e), f).clone(memory_format=torch.contiguous_format)
+    bb = _gmm_operand("probe_fit", "b", b, (c,), f).clone(memory_format=torch.contiguous_format)
+    scale, lr = _probe_scalar("probe_fit", "scale", scale), _probe_scalar("probe_fit", "lr", lr)
+    l2, momentum = _probe_scalar("probe_fit", "l2", l2, positive=False), _probe_scalar("probe_fit", "momentum", momentum, positive=False)
+    if momentum >= 1 or int(iters) < 1:
+        raise native.GripError(f"probe_fit: momentum = {momentum:g}, iters = {iters} (0 <= momentum < 1, iters >= 1)")
+    lib = native.lib()
+    if state is None:
+        mw, mb, ws = torch.zeros_like(ww), torch.zeros_like(bb), _gda_workspace(lib.grip_probe_fit_workspace, (n, c, e), f.device)
+    else:
+        mw = _gmm_operand("probe_fit", "state[0]", state[0], (c, e), f).clone(memory_format=torch.contiguous_format)
+        mb = _gmm_operand("probe_fit", "state[1]", state[1], (c,), f).clone(memory_format=torch.contiguous_format)
+        ws = state[3]
+        norm = state[2] if norm is None else norm
+    norm = _probe_scalar("probe_fit", "norm", probe_norm(y, sf, r, c) if norm is None else norm)
+    trace = torch.empty(int(iters), dtype=torch.float32, device=f.device) if want_trace else None
+    native.check(lib.grip_probe_fit(_ptr(f), _ptr(bs), _ptr(y), _ptr(sf), _ptr(r), scale, norm, l2, lr, momentum, int(iters), n, c, e, _ptr(ww), _ptr(bb),
+                                    _ptr(mw), _ptr(mb), _ptr(trace), _ptr(ws), ws.numel(), _stream()))
+    state = (mw, mb, norm, ws)
+    return (ww, bb, state, trace) if want_trace else (ww, bb, state)
+
+
 SINKHORN_ROWS = 16      # csrc/sinkhorn.hip: SK_ROWS, the fixed row partition of the column sums
 
 

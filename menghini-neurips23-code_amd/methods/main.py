@@ -118,7 +118,8 @@ def workflow(obj_conf, device, n_synth, n_classes=10):
     else:
         val_acc, prompt = getattr(model, method)(train_data, val_data, unlabeled_data, only_seen=only_seen)
     # methods/main_SSL.py:400 (+ the Tip-Adapter cache file with TIP_ADAPTER, the CLIP-Adapter file with CLIP_ADAPTER)
-    save_parameters(prompt, obj_conf, cache=getattr(model, "tip", None), adapter=getattr(model, "adapter", None), gda=getattr(model, "gda", None))
+    save_parameters(prompt, obj_conf, cache=getattr(model, "tip", None), adapter=getattr(model, "adapter", None), gda=getattr(model, "gda", None),
+                    probe=getattr(model, "probe", None))
     df = model.test_predictions(test_data, standard_zsl=False)
     truth = {files[i]: names[i] for i in test_ids}
     std_response = evaluate_predictions(obj_conf, df, [files[i] for i in test_ids], [names[i] for i in test_ids], unseen, seen)   # methods/main_SSL.py:404-414

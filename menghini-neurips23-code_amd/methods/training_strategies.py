@@ -18,8 +18,8 @@ import numpy as np
 import torch
 
 from .. import clip, dist as gdist, pseudolabels as pl, steps
-from ..engine import cosine_head
-from ..models import ClipAdapterModel, CustomImageEncoder, CustomTextEncoder, GdaHeadModel, ImagePrefixModel, MaPLeModel, TextPrefixModel, TipAdapterModel, UPTModel
+from ..engine import cosine_head, soft_ce
+from ..models import ClipAdapterModel, CustomImageEncoder, CustomTextEncoder, GdaHeadModel, ImagePrefixModel, LinearProbeModel, MaPLeModel, TextPrefixModel, TipAdapterModel, UPTModel
 from ..utils import pseudolabel_top_k
 
 log = logging.getLogger(__name__)
@@ -74,6 +74,12 @@ class TrainingStrategy:
         if bool(getattr(config, "GDA_HEAD", False)) and self.modality != "text":
             log.info(f"GDA_HEAD is ignored by the {self.modality} strategies: their image features move with the prompt (textual strategies only)")
         self.gda_head()          # (raises when GDA_HEAD is set together with TIP_ADAPTER or CLIP_ADAPTER)
+        # LINEAR_PROBE (textual strategies): the linear classifier trained on the cached training features after each prompt training
+        # (build_linear_probe); None = off
+        self.probe, self.probe_classes, self.probe_search, self.probe_targets = None, None, None, None
+        if bool(getattr(config, "LINEAR_PROBE", False)) and self.modality != "text":
+            log.info(f"LINEAR_PROBE is ignored by the {self.modality} strategies: their image features move with the prompt (textual strategies only)")
+        self.linear_probe()      # (raises when LINEAR_PROBE is set together with TIP_ADAPTER, CLIP_ADAPTER or GDA_HEAD)
         # LABEL_PROPAGATION (all modalities, default False): every pseudolabel pass propagates the head's probabilities over the pool's kNN graph
         # (LP_K 16, LP_ALPHA 0.8, LP_GAMMA 10, LP_ITERS 10: untuned).  Textual strategies keep the graph per pool -- their image tower is frozen, the graph
         # is an invariant of the run; visual and multimodal strategies rebuild it every pass: their features move with the prompt.
@@ -222,11 +228,26 @@ class TrainingStrategy:
             raise ValueError("GDA_HEAD, TIP_ADAPTER and CLIP_ADAPTER are different heads on the same image features: set one of them")
         return on
 
+    def linear_probe(self):
+        """Trained linear probe for the textual strategies: config LINEAR_PROBE, default False (PROBE_ITERS 300, PROBE_MOMENTUM 0.9, PROBE_L2 0.1,
+        PROBE_ALPHA 1.0, PROBE_PSEUDO_WEIGHT 1.0, PROBE_SEARCH False, PROBE_ALPHA_GRID (0.1, 0.3, 1, 3, 10), PROBE_INIT "zero" or "gda" -- which reads
+        GDA_SHRINK: untuned).  Their image tower is frozen and their training features are cached, so the probe trains without a tower pass.  Visual
+        and multimodal strategies ignore it, as they ignore GDA_HEAD.  Together with TIP_ADAPTER, CLIP_ADAPTER or GDA_HEAD it is refused: they are
+        different heads on the same features, and stacking them is not defined here."""
+        on = self.modality == "text" and bool(getattr(self.config, "LINEAR_PROBE", False))
+        others = [k for k in ("TIP_ADAPTER", "CLIP_ADAPTER", "GDA_HEAD") if bool(getattr(self.config, k, False))]
+        if on and others:
+            raise ValueError(f"LINEAR_PROBE and {' and '.join(others)} are different heads on the same image features: set one of them")
+        if on and str(getattr(self.config, "PROBE_INIT", "zero")) not in ("zero", "gda"):
+            raise ValueError(f"PROBE_INIT: {getattr(self.config, 'PROBE_INIT')!r} (\"zero\" or \"gda\")")
+        return on
+
     def define_model(self, classes=None):
         c, dev = self.config, self.device
         self.tip = None      # a cache belongs to the prompt it was built after: validation during the next training sees CLIP logits alone
         self.adapter = None  # and so does a feature adapter
         self.gda = None      # and a discriminant head
+        self.probe = None    # and a trained linear probe
         classes = classes if classes is not None else self.classes
         if self.modality == "text":
             deep = getattr(self, "initial_deep_prefix", None)
@@ -542,6 +563,8 @@ class TrainingStrategy:
                 logits = self._add_cache_term(image_features, logits, classes)
             if self.gda is not None:      # GDA_HEAD: the discriminant term of the iteration's training set
                 logits = self._add_gda_term(image_features, logits, classes)
+            if self.probe is not None:    # LINEAR_PROBE: the trained residual of the iteration's training set
+                logits = self._add_probe_term(image_features, logits, classes)
             outs.append(logits)
         logits = torch.cat(outs) if outs else torch.empty(0, len(classes), device=self.device)
         logits = gdist.gather_in_dataset_order(logits, len(data), int(self.config.BATCH_SIZE))
@@ -570,6 +593,8 @@ class TrainingStrategy:
             self.build_feature_adapter(train_data, val_data, only_seen=only_seen)
         if self.gda_head():
             self.build_gda_head(train_data, val_data, only_seen=only_seen)
+        if self.linear_probe():
+            self.build_linear_probe(train_data, val_data, only_seen=only_seen)
         return best_acc, best_prompt
 
     # ------------------------------------------------------------------ Tip-Adapter cache (TIP_ADAPTER, textual strategies)
@@ -746,6 +771,72 @@ class TrainingStrategy:
             logits[:, dst] += term[:, src]
         return logits
 
+    # ------------------------------------------------------------------ trained linear probe (LINEAR_PROBE, textual strategies)
+    def build_linear_probe(self, train_data, val_data=None, only_seen=False):
+        """The linear probe of the iteration just trained: models.LinearProbeModel.fit on the training set's cached frozen features (labelled shots and
+        pseudolabelled pool rows: the rows the prompt steps read; a pseudolabelled row weighs PROBE_PSEUDO_WEIGHT) against the CLIP logits of the prompt
+        just trained -- a residual on them that starts at zero (PROBE_INIT "gda": at the Gaussian discriminant head of the same rows, ridge GDA_SHRINK) --
+        for PROBE_ITERS full-batch heavy-ball iterations (PROBE_MOMENTUM, ridge PROBE_L2, the step from the Lipschitz bound).  With SOFT_PSEUDOLABELS
+        the pseudolabelled rows train on the targets engine.soft_ce builds for them from the last pass's matrix (the sharpening is that kernel's, not
+        restated here); every other row is hard.  PROBE_SEARCH picks alpha from PROBE_ALPHA_GRID on the validation set.  From here on predict() --
+        hence _run_validation, test_predictions and evaluation -- adds alpha * (scale * normalize(f) . W_c + b_c) to the logits it computes.
+
+        The pseudolabel pass is NOT touched: assign_pseudo_labels and the frozen-CLIP pass keep ranking the pool by the CLIP logits of the prompts
+        alone, so pseudolabel lists and prompt files are the same with the switch on or off."""
+        c = self.config
+        classes, ids, lut = self._class_space(only_seen)
+        with torch.random.fork_rng(devices=[]):      # (_tip_inputs' DataLoader draws its base seed from the global stream: see build_feature_adapter)
+            feats, clip_logits, labs, names = self._tip_inputs(train_data, classes, lut)
+        pseudo = [getattr(self, "fpl", False) and (self.paradigm == "ul" or n in self.check_unlabeled) for n in names]
+        labels, targets = labs, None
+        soft = self.soft_targets(classes, only_seen)
+        rows = self.soft_rows(soft, ids[labs].tolist(), names) if soft is not None else None
+        if rows is not None:
+            _, _, targets = soft_ce(clip_logits, labs, torch.ones(len(names), device=self.device), soft.matrix, rows, soft.col_map, soft.temperature,
+                                    soft.smoothing, want_target=True)
+            labels = torch.where(rows.to(labs.device) >= 0, torch.full_like(labs, -1), labs)
+        self.probe_targets = (labels, targets)      # (what the fit was given: the rows with label -1 train on their row of targets)
+        init = None
+        scale = float(self.scale())
+        if str(getattr(c, "PROBE_INIT", "zero")) == "gda":
+            g = GdaHeadModel.fit(feats, labs, pseudo, len(classes), pseudo_weight=float(getattr(c, "PROBE_PSEUDO_WEIGHT", 1.0)),
+                                 shrink=float(getattr(c, "GDA_SHRINK", 1.0)))
+            init = (g.w / scale, -g.bias)
+        self.probe = LinearProbeModel.fit(feats, clip_logits, labels, pseudo, len(classes), soft=targets,
+                                          pseudo_weight=float(getattr(c, "PROBE_PSEUDO_WEIGHT", 1.0)), scale=scale, l2=float(getattr(c, "PROBE_L2", 0.1)),
+                                          iters=int(getattr(c, "PROBE_ITERS", 300)), momentum=float(getattr(c, "PROBE_MOMENTUM", 0.9)),
+                                          alpha=float(getattr(c, "PROBE_ALPHA", 1.0)), init=init)
+        self.probe_classes, self.probe_search = list(classes), None
+        trace = self.probe.loss_trace
+        log.info(f"linear probe: {trace.numel()} iterations over {len(names)} rows, loss {float(trace[0]):.4f} -> {float(trace[-1]):.4f} (at the start of the last)")
+        if bool(getattr(c, "PROBE_SEARCH", False)) and val_data is not None and len(val_data):
+            with torch.random.fork_rng(devices=[]):
+                vf, vl, vy, _ = self._tip_inputs(val_data, classes, lut)
+            if len(vy):
+                self.probe_search = self.probe.search(list(getattr(c, "PROBE_ALPHA_GRID", (0.1, 0.3, 1.0, 3.0, 10.0))), vf, vl, vy)
+                log.info(f"linear probe search: alpha {self.probe_search[0]:g} (validation accuracy {self.probe_search[1]:.3f})")
+        return self.probe
+
+    def load_linear_probe(self, path, classes=None):
+        """Install a head file written by utils.save_parameters(..., probe=strategy.probe); `classes`: its class list (default: all classes)."""
+        self.probe = LinearProbeModel.load(path, device=self.device)
+        self.probe_classes = list(classes if classes is not None else self.classes)
+        return self.probe
+
+    @torch.no_grad()
+    def _add_probe_term(self, image_features, logits, classes):
+        """logits [N, len(classes)] + the probe's term of the columns it knows (all of them when `classes` is the probe's own list: one launch;
+        otherwise the term is computed against no base and its columns are gathered), as _add_gda_term does for the discriminant head."""
+        if list(classes) == self.probe_classes:
+            return self.probe(image_features, logits)
+        term = self.probe(image_features, torch.zeros(logits.shape[0], len(self.probe_classes), device=logits.device))
+        pos = {c: i for i, c in enumerate(self.probe_classes)}
+        cols = [(j, pos[c]) for j, c in enumerate(classes) if c in pos]
+        if cols:
+            dst, src = (torch.tensor(x, device=logits.device) for x in zip(*cols))
+            logits[:, dst] += term[:, src]
+        return logits
+
     # ------------------------------------------------------------------ evaluation
     def test_predictions(self, data, standard_zsl=False):
         import pandas as pd
@@ -872,7 +963,7 @@ class TrainingStrategy:
             out = self.train(data, val_data, only_seen=only_seen, iter_train=True)
             from ..utils import save_parameters, save_pseudo_labels
             save_pseudo_labels(list(data.filepaths), list(data.labels), c, niter)     # compute_metrics.py:150-154
-            save_parameters(out[1], c, iteration=niter, cache=self.tip, adapter=self.adapter, gda=self.gda)
+            save_parameters(out[1], c, iteration=niter, cache=self.tip, adapter=self.adapter, gda=self.gda, probe=self.probe)
             log.info(f"GRIP iteration {niter}/{num_iter}: {c.N_PSEUDOSHOTS} pseudo-shots per class, val acc {out[0]:.3f}")
         return out
 

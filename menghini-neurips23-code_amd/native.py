@@ -113,6 +113,13 @@ _SIGS = {
     "grip_spd_solve": (c_int, [c_void_p, c_float, c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "grip_linear_head_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
     "grip_linear_head": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # (ABI 9 additions) trained linear probe: loss + gradient of a softmax classifier over cached features, and the heavy-ball fit (csrc/linear_probe.hip)
+    "grip_probe_objective_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "grip_probe_objective": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_int, c_int, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "grip_probe_fit_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "grip_probe_fit": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_int, c_int, c_int, c_int,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     # (ABI 9 additions) balanced (Sinkhorn-Knopp) assignment of a pool's probabilities to a class prior (csrc/sinkhorn.hip)
     "grip_sinkhorn_workspace": (c_int, [c_int, c_int, POINTER(c_size_t)]),
     "grip_sinkhorn_balance": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,

@@ -72,7 +72,12 @@ def gda_head_path(config, iteration=None):
     return _prompt_base(config, iteration) + "_gda.pickle"
 
 
-def save_parameters(obj, config, iteration=None, cache=None, adapter=None, gda=None):
+def linear_probe_path(config, iteration=None):
+    """The trained linear probe file of a run (LINEAR_PROBE), beside its prompt file."""
+    return _prompt_base(config, iteration) + "_probe.pickle"
+
+
+def save_parameters(obj, config, iteration=None, cache=None, adapter=None, gda=None, probe=None):
     """utils/compute_metrics.py:105-147 of the reference.  Textual / visual prompts: `obj` (a list holding the prompt as a
     numpy array) pickled to `{base}.pickle`.  MODALITY == "multi": `obj` is the positional list of the eight trainable pieces
     (UPT_NAMES order, methods/*/multimodal_prompt.py:149-158) and each goes to its own file -- the five state_dicts with
@@ -81,7 +86,8 @@ def save_parameters(obj, config, iteration=None, cache=None, adapter=None, gda=N
     `cache` (a models.TipAdapterModel, the strategy's `tip`; TIP_ADAPTER) goes to a file of its own, `{base}_tip.pickle` (tip_cache_path): keys, class
     ids, key weights and hyperparameters -- the prompt file and the return value are what they are without it.  `adapter` (a
     models.ClipAdapterModel, the strategy's `adapter`; CLIP_ADAPTER) likewise goes to `{base}_adapter.pickle` (adapter_path): w1, w2, ratio; `gda` (a
-    models.GdaHeadModel, the strategy's `gda`; GDA_HEAD) to `{base}_gda.pickle` (gda_head_path): mean, w, bias, alpha."""
+    models.GdaHeadModel, the strategy's `gda`; GDA_HEAD) to `{base}_gda.pickle` (gda_head_path): mean, w, bias, alpha; `probe` (a models.LinearProbeModel, the strategy's
+    `probe`; LINEAR_PROBE) to `{base}_probe.pickle` (linear_probe_path): w, b, scale, alpha."""
     os.makedirs("trained_prompts", exist_ok=True)
     base = _prompt_base(config, iteration)
     if cache is not None:
@@ -90,6 +96,8 @@ def save_parameters(obj, config, iteration=None, cache=None, adapter=None, gda=N
         adapter.save(base + "_adapter.pickle")
     if gda is not None:
         gda.save(base + "_gda.pickle")
+    if probe is not None:
+        probe.save(base + "_probe.pickle")
     if getattr(config, "MODALITY", None) == "multi" and getattr(config, "MAPLE", False):
         # MaPLe: [ctx, compound_prompts_text, proj_weight, proj_bias] as numpy (TrainingStrategy.prompt_snapshot), one pickle
         with open(base + "_maple.pickle", "wb") as f:
