@@ -546,6 +546,46 @@ int grip_soft_ce(const float* logits, const int32_t* labels, const float* row_we
                  float* target_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 9 additions) Candidate pseudolabel SETS over a pool and the partial-label loss on them (pseudolabels.CandidateSelection; csrc/candidate.hip;
+ * Candidate Pseudolabel Learning, Zhang, Wei, Liu, Feng, ICML 2024): every image keeps a set of classes instead of one label.
+ *   probs [n, c] f32: finite and >= 0 is the CALLER's duty (non-negative floats order as their bit patterns, which the selection relies on).
+ *   claim in [1, n]: the rows every class claims.  tau in (0, 1].  combine: 0 intersection, 1 union, 2 intra only, 3 inter only.
+ *   threshold [c] f32 = the claim-th largest value of column c, EXACT (a radix select over the bit patterns, four passes of 8 bits; the digit counts are
+ *   integers, so no order of accumulation can change a bit).
+ *   INTER set of row i: { c : probs[i, c] >= threshold[c] } -- ties at the threshold are all in.
+ *   INTRA set of row i: rank the classes by probability descending, index ascending; s_0 = p_(0), s_j = s_{j-1} + p_(j) (plain f32 additions in rank
+ *   order, no fused multiply-add, no reassociation); rank 0 is always in, rank j >= 1 is in iff s_{j-1} < tau.
+ *   mask [n, words] int32, words = ceil(c / 32): class j is bit j % 32 of word j / 32; the bits at or above c are 0.
+ *   count [n] int32 = the set's size; label [n] int32 = its member of highest rank, -1 for an empty set.
+ *   threshold, count and label may each be NULL.  Any n >= 1, any c >= 1 (up to 256 classes a row is held in registers, beyond it is re-read).
+ * Two calls are bit-equal.  Given threshold, a row's mask, count and label depend on that row alone -- not on n, not on its place.  No scratch.  One call
+ * enqueues 10 launches whatever (n, c); the workspace (grip_candidate_select_workspace bytes: the digit histograms, c KiB) is overwritten; the workspace
+ * call needs no device.  Out-of-range arguments (n, c, claim, tau, combine, a null probs / mask / workspace, a small workspace) are refused with nothing
+ * written.
+ *
+ * grip_candidate_ce: grip_weighted_ce for batches whose rows may carry a candidate set (one workgroup, a wave per row, no atomics, no scratch, no
+ * workspace).
+ *   logits [n, c], labels [n] int32, row_weight [n]: as grip_weighted_ce.
+ *   cand [cand_rows, ceil(cz / 32)] int32: the mask matrix of grip_candidate_select over cz classes, read in place (NULL: every row is a hard row;
+ *   cand_row and col_map may then be NULL).
+ *   cand_row [n] int32: the mask row of batch row i; a value outside [0, cand_rows) marks a HARD row (its label is the target).
+ *   col_map [cz] int32: the logits column of every mask column, as grip_soft_ce: distinct entries in [0, c) are the caller's contract, an entry outside
+ *   [0, c) is skipped, never indexed.
+ * A candidate row with mapped set S = { col_map[j] : bit j set, col_map[j] in [0, c) }:
+ *   loss_i = w_i (lse(x_i) - lse_{k in S}(x_ik)),        grad_i = w_i (softmax(x_i) - softmax_S(x_i)),  softmax_S zero outside S
+ * (lse_S = max_S + logf(sum_S expf(x - max_S)); its label is not read).  A candidate row whose mapped set is EMPTY contributes nothing: no loss, a zero
+ * gradient row.  Hard rows run grip_weighted_ce's statements and the loss partials are added in its order: with cand == NULL the loss and every gradient
+ * element are grip_weighted_ce's bits.  A candidate row whose set is the single class y gives the bits of a hard row with label y.  loss [1]; grad_logits
+ * may be NULL.  Two calls are bit-equal; a row's bits depend on that row, its mask row and col_map alone.
+ * Refused with nothing written: a null operand, n or c <= 0, cz outside [1, c] with cand given, and c > 16000 with cand given (the inverse of col_map
+ * is held in the LDS). */
+int grip_candidate_select_workspace(int n, int c, size_t* bytes);
+int grip_candidate_select(const float* probs, int n, int c, int claim, float tau, int combine, float* threshold, int32_t* mask, int32_t* count,
+                          int32_t* label, void* workspace, size_t workspace_bytes, void* stream);
+int grip_candidate_ce(const float* logits, const int32_t* labels, const float* row_weight, int n, int c, const int32_t* cand, int64_t cand_rows, int cz,
+                      const int32_t* cand_row, const int32_t* col_map, float* loss, float* grad_logits, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CLIP preprocessing of one decoded image: the `_transform` the reference applies per item on the host
  * (data/dataset.py:64-79 via clip.load's preprocess): Resize(n_px, BICUBIC) -> CenterCrop(n_px) -> ToTensor -> Normalize.
  * Bit-exact with Pillow's 8-bit bicubic resample; only the cropped rows / columns are produced.

@@ -587,7 +587,7 @@ class WeightedCEFn(torch.autograd.Function):
 _COL_MAPS_OK = []       # [(weakref of a col_map tensor, its version counter, c)] that passed the host check of soft_ce, most recent first
 
 
-def _check_col_map(col_map, c):
+def _check_col_map(col_map, c, who="soft_ce"):
     """col_map (int32 [cz] on the device) is injective into [0, c): checked on the host ONCE per tensor (and per version of it) -- a later call with the
     same tensor costs no device read, so a step may run under graph capture once its warm-up has passed here."""
     import weakref
@@ -597,7 +597,7 @@ def _check_col_map(col_map, c):
             return
     host = col_map.cpu()
     if host.numel() and (int(host.min()) < 0 or int(host.max()) >= c or torch.unique(host).numel() != host.numel()):
-        raise native.GripError(f"soft_ce: col_map must hold distinct logits columns in [0, {c}), got {host.tolist()}")
+        raise native.GripError(f"{who}: col_map must hold distinct logits columns in [0, {c}), got {host.tolist()}")
     _COL_MAPS_OK.insert(0, (weakref.ref(col_map), col_map._version, c))
     del _COL_MAPS_OK[8:]
 
@@ -659,6 +659,98 @@ class SoftCEFn(torch.autograd.Function):
     def backward(ctx, g):
         (grad,) = ctx.saved_tensors
         return (grad * g,) + (None,) * 7
+
+
+CANDIDATE_COMBINE = {"intersection": 0, "union": 1, "intra": 2, "inter": 3}      # grip_candidate_select's combine
+
+
+def candidate_select(probs, claim, tau=0.99, combine="intersection"):
+    """(mask int32 [n, ceil(c / 32)], count int32 [n], label int32 [n], threshold f32 [c]): the candidate pseudolabel sets of include/grip_amd.h on the
+    native kernels (csrc/candidate.hip).  threshold[c] is the claim-th largest value of column c, exact; the INTER set of a row holds the classes whose
+    threshold the row reaches, the INTRA set the smallest prefix of its classes (probability descending, index ascending) whose f32 running sum reaches
+    tau; `combine` ("intersection", "union", "intra", "inter") joins them.  Class j is bit j % 32 of mask word j // 32; label is the member of highest
+    rank, -1 for an empty set.  probs must be finite and >= 0.  Bit-identical from call to call."""
+    if not torch.is_tensor(probs) or probs.dim() != 2 or not probs.is_floating_point():
+        raise native.GripError(f"candidate_select: probs must be a floating-point [n, c] tensor, got {getattr(probs, 'shape', type(probs))}")
+    n, c = probs.shape
+    require_gpu(probs.device)
+    if combine not in CANDIDATE_COMBINE:
+        raise native.GripError(f"candidate_select: combine = {combine!r} (one of {sorted(CANDIDATE_COMBINE)})")
+    if isinstance(claim, bool) or not isinstance(claim, int) or not 1 <= claim <= max(n, 1):
+        raise native.GripError(f"candidate_select: claim = {claim!r} (an integer in [1, n = {n}])")
+    if not 0.0 < float(tau) <= 1.0:
+        raise native.GripError(f"candidate_select: tau = {tau} (in (0, 1])")
+    p = probs.detach().contiguous().float()
+    lib = native.lib()
+    nbytes = c_size_t()
+    native.check(lib.grip_candidate_select_workspace(n, c, byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=p.device)
+    mask = torch.empty(n, (c + 31) // 32, dtype=torch.int32, device=p.device)
+    count = torch.empty(n, dtype=torch.int32, device=p.device)
+    label = torch.empty(n, dtype=torch.int32, device=p.device)
+    threshold = torch.empty(c, dtype=torch.float32, device=p.device)
+    native.check(lib.grip_candidate_select(_ptr(p), n, c, int(claim), float(tau), CANDIDATE_COMBINE[combine], _ptr(threshold), _ptr(mask), _ptr(count),
+                                           _ptr(label), _ptr(ws), ws.numel(), _stream()))
+    return mask, count, label, threshold
+
+
+def candidate_ce(logits, labels, row_weight, cand=None, cand_row=None, col_map=None):
+    """(loss, grad) of the weighted partial-label cross-entropy (csrc/candidate.hip, grip_candidate_ce): batch row i with 0 <= cand_row[i] < cand.shape[0]
+    trains on the candidate SET in that row of the mask matrix `cand` (int32 [rows, ceil(cz / 32)], candidate_select's layout; mask column j is logits
+    column col_map[j]): loss_i = w_i (lse(x_i) - lse_S(x_i)), grad_i = w_i (softmax(x_i) - softmax_S(x_i)); an empty set contributes nothing.  Every other
+    row trains on labels[i] as grip_weighted_ce does.  loss: 0-d f32; grad [n, c].  `cand` is read in place.  cand=None gives grip_weighted_ce's bits.
+    No autograd (CandidateCEFn)."""
+    lib = native.lib()
+    if not torch.is_tensor(logits) or logits.dim() != 2 or not logits.is_cuda:
+        raise native.GripError(f"candidate_ce: logits must be a [n, c] tensor on the GPU, got {getattr(logits, 'shape', type(logits))}")
+    lg = logits.detach().contiguous().float()
+    n, c = lg.shape
+    dev = lg.device
+    if not torch.is_tensor(labels) or tuple(labels.shape) != (n,) or labels.dtype.is_floating_point:
+        raise native.GripError(f"candidate_ce: labels must be an integer [{n}] tensor, got {getattr(labels, 'shape', type(labels))} "
+                               f"{getattr(labels, 'dtype', None)}")
+    if not torch.is_tensor(row_weight) or tuple(row_weight.shape) != (n,) or not row_weight.dtype.is_floating_point:
+        raise native.GripError(f"candidate_ce: row_weight must be a floating-point [{n}] tensor, got {getattr(row_weight, 'shape', type(row_weight))}")
+    lab = labels.to(device=dev, dtype=torch.int32).contiguous()
+    w = row_weight.to(device=dev, dtype=torch.float32).contiguous()
+    rows = cz = 0
+    if cand is not None:
+        if not torch.is_tensor(col_map) or col_map.dim() != 1 or col_map.dtype != torch.int32 or col_map.device != dev or not col_map.is_contiguous():
+            raise native.GripError(f"candidate_ce: col_map must be a contiguous int32 [cz] tensor on {dev}, got {getattr(col_map, 'shape', type(col_map))} "
+                                   f"{getattr(col_map, 'dtype', None)}")
+        cz = col_map.shape[0]
+        if not 1 <= cz <= c:
+            raise native.GripError(f"candidate_ce: col_map names {cz} mask columns for {c} logits columns (1 .. c)")
+        words = (cz + 31) // 32
+        if not torch.is_tensor(cand) or cand.dim() != 2 or cand.shape[1] != words or cand.dtype != torch.int32 or cand.device != dev or not cand.is_contiguous():
+            raise native.GripError(f"candidate_ce: cand must be a contiguous int32 [rows, {words}] tensor on {dev} (it is read in place), got "
+                                   f"{getattr(cand, 'shape', type(cand))} {getattr(cand, 'dtype', None)} on {getattr(cand, 'device', None)}")
+        rows = cand.shape[0]
+        cand_row = _gmm_operand("candidate_ce", "cand_row", cand_row, (n,), lg, torch.int32)
+        _check_col_map(col_map, c, "candidate_ce")
+    else:
+        cand_row = col_map = None
+    loss = torch.zeros(1, dtype=torch.float32, device=dev)
+    grad = torch.empty_like(lg)
+    native.check(lib.grip_candidate_ce(_ptr(lg), _ptr(lab), _ptr(w), n, c, _ptr(cand), rows, cz, _ptr(cand_row), _ptr(col_map), _ptr(loss), _ptr(grad),
+                                       _stream()))
+    return loss[0], grad
+
+
+class CandidateCEFn(torch.autograd.Function):
+    """SoftCEFn's twin on candidate sets: sum_i w_i (lse(x_i) - lse_S(x_i)) of engine.candidate_ce, native forward + backward (one kernel produces both).
+    apply(logits, labels, row_weight, cand, cand_row, col_map)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, row_weight, cand, cand_row, col_map):
+        loss, grad = candidate_ce(logits, labels, row_weight, cand, cand_row, col_map)
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad * g,) + (None,) * 5
 
 
 class UptMixerFn(torch.autograd.Function):

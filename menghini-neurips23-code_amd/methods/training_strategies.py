@@ -122,6 +122,21 @@ class TrainingStrategy:
             if not 0.0 < self.soft_temperature < float("inf"):
                 raise ValueError(f"SOFT_TEMPERATURE: {self.soft_temperature} (a finite temperature > 0)")
             self.soft_store = pl.SoftTargetStore()
+        # CANDIDATE_PSEUDOLABELS (all modalities and paradigms, default False; CPL_TAU 0.99, CPL_SLOTS 2, CPL_COMBINE "intersection": untuned): every
+        # pseudolabel pass keeps a SET of classes per pool image instead of one label (pl.CandidateSelection -> engine.candidate_select, on the matrix
+        # the pass would have ranked: Z / Q of the transductions above, else the head's probabilities; each class claims CPL_SLOTS x N_PSEUDOSHOTS rows)
+        # and every pseudolabelled row of a prompt step trains on -log sum_{c in S} p_c (pl.CandidateStore -> engine.candidate_ce); labelled rows keep
+        # their one-hot.  The training list is every pool row with a non-empty set, once, labelled with the set's first member: row_weights, the epoch
+        # accuracy, the held-out pseudolabel validation, `predict`, the Tip cache, the adapter, GDA and the probe see that hard label.  Fixed soft rows
+        # and smoothing are other targets for the same rows: not composed.
+        self.candidate_selection = self.candidate_store = None
+        if bool(getattr(config, "CANDIDATE_PSEUDOLABELS", False)):
+            if bool(getattr(config, "SOFT_PSEUDOLABELS", False)) or self.label_smoothing > 0.0:
+                raise ValueError("CANDIDATE_PSEUDOLABELS trains the pseudolabelled rows on candidate sets: SOFT_PSEUDOLABELS and LABEL_SMOOTHING > 0 give "
+                                 "the same rows other targets (these compositions are not built): set one of them")
+            self.candidate_selection = pl.CandidateSelection(tau=float(getattr(config, "CPL_TAU", 0.99)), slots=getattr(config, "CPL_SLOTS", 2),
+                                                             combine=getattr(config, "CPL_COMBINE", "intersection"))
+            self.candidate_store = pl.CandidateStore()
         self.declare_custom_encoder()
         self.initialize_prompts_parameters()
 
@@ -350,7 +365,8 @@ class TrainingStrategy:
         c = self.config
         pseudo_classes = self.classes if self.paradigm in ("ssl", "ul") else self.unseen_classes
         # the frozen-CLIP pass runs the same towers over the same pool as the trained-prompt passes after it
-        with pl.pool_cache(self.pool_cache), pl.label_propagation(self.transduction()), pl.soft_targets(self.soft_store):
+        with pl.pool_cache(self.pool_cache), pl.label_propagation(self.transduction()), pl.soft_targets(self.soft_store), \
+                pl.candidate_sets(self.candidate_selection, self.candidate_store):
             pseudolabel_top_k(c, c.DATASET_NAME, int(c.N_PSEUDOSHOTS), self.template, unlabeled_data, pseudo_classes, self.transform,
                               self.clip_model, self.label_to_idx, self.device, c.VIS_ENCODER, getattr(c, "SPLIT_SEED", 0))
         return self.merge_pseudolabels(train_data, unlabeled_data)
@@ -394,9 +410,13 @@ class TrainingStrategy:
         return steps.fpl_row_weights([int(l) in unseen_ids for l in labels], gamma_seen=1.0, gamma_pseudo=self.balance_param)
 
     def soft_targets(self, classes, only_seen=False):
-        """The steps.SoftTargets of an epoch over `classes`, or None (both switches absent: the steps call WeightedCEFn exactly as before).  The matrix
+        """The steps.SoftTargets (or, with CANDIDATE_PSEUDOLABELS, the steps.CandidateTargets) of an epoch over `classes`, or None (every switch absent:
+        the steps call WeightedCEFn exactly as before).  The matrix
         is the one the last pseudolabel pass recorded (SOFT_PSEUDOLABELS; none for only_seen training, which has no pseudolabelled rows, and before a
         pass has recorded one); LABEL_SMOOTHING alone gives a SoftTargets without a matrix."""
+        cand = None if only_seen else self.candidate_store
+        if cand is not None and cand.mask is not None:      # (CANDIDATE_PSEUDOLABELS: the sets of the last pass; excludes the two switches below)
+            return steps.CandidateTargets(cand.mask, cand.col_map([self.label_to_idx[c] for c in classes]))
         store = None if only_seen else self.soft_store
         if store is not None and store.matrix is not None:
             ids = [self.label_to_idx[c] for c in classes]
@@ -413,7 +433,8 @@ class TrainingStrategy:
             pseudo = [int(l) in unseen_ids for l in labels]
         else:
             pseudo = [n in self.check_unlabeled for n in names]
-        return self.soft_store.rows(list(names), hard=[not p for p in pseudo])      # (built on the host, one upload: no synchronisation)
+        store = self.candidate_store if isinstance(soft, steps.CandidateTargets) else self.soft_store
+        return store.rows(list(names), hard=[not p for p in pseudo])      # (built on the host, one upload: no synchronisation)
 
     # ------------------------------------------------------------------ loops
     def _loader(self, data, shuffle):
@@ -790,6 +811,8 @@ class TrainingStrategy:
         pseudo = [getattr(self, "fpl", False) and (self.paradigm == "ul" or n in self.check_unlabeled) for n in names]
         labels, targets = labs, None
         soft = self.soft_targets(classes, only_seen)
+        if isinstance(soft, steps.CandidateTargets):
+            soft = None         # (CANDIDATE_PSEUDOLABELS: the probe keeps the hard label of every set)
         rows = self.soft_rows(soft, ids[labs].tolist(), names) if soft is not None else None
         if rows is not None:
             _, _, targets = soft_ce(clip_logits, labs, torch.ones(len(names), device=self.device), soft.matrix, rows, soft.col_map, soft.temperature,
@@ -917,10 +940,13 @@ class TrainingStrategy:
         images = _pool_images(unlabeled_data, self.transform, self.device)
         labels = [self.label_to_idx[c] for c in classes]
         paths = list(unlabeled_data.filepaths)      # the pool as passed to the pass (grip_train resets it to the original list every iteration): the cache's key
-        with pl.pool_cache(self.pool_cache), pl.label_propagation(self.transduction()), pl.soft_targets(self.soft_store):       # (None: nothing is installed)
+        with pl.pool_cache(self.pool_cache), pl.label_propagation(self.transduction()), pl.soft_targets(self.soft_store), \
+                pl.candidate_sets(self.candidate_selection, self.candidate_store):       # (None: nothing is installed)
             if pl.propagation() is not None:
                 log.info(f"{pl.propagation()} is installed: the pass propagates over the pool and takes the plain branch (no reference list to be identical to)")
-            if pl.mode() == "identical" and pl.propagation() is None and not self.clip_model.exact:
+            if pl.candidates() is not None:
+                log.info(f"{pl.candidates()[0]} is installed: the pass selects candidate sets and takes the plain branch (no reference list to be identical to)")
+            if pl.mode() == "identical" and pl.propagation() is None and pl.candidates() is None and not self.clip_model.exact:
                 # the lists the reference's fp32 pass would produce with these prompts: f16 screen + exact refinement
                 twin = self.clip_model.exact_twin()
                 txt, vprompt = self.trained_text_features(classes, twin)

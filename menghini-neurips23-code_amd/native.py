@@ -127,6 +127,10 @@ _SIGS = {
     # (ABI 9 addition) weighted cross-entropy against soft targets gathered from a pool's assignment matrix (csrc/soft_ce.hip)
     "grip_soft_ce": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p,
                              c_void_p, c_void_p]),
+    # (ABI 9 additions) candidate pseudolabel sets over a pool and the partial-label loss on them (csrc/candidate.hip)
+    "grip_candidate_select_workspace": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "grip_candidate_select": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "grip_candidate_ce": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "grip_preprocess_image": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                       c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "grip_preprocess_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

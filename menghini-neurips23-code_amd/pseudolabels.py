@@ -1072,31 +1072,27 @@ def propagation():
 
 
 # ------------------------------------------------------------------------------------------ from the pass to the step: the matrix behind the lists
-class SoftTargetStore:
-    """Keeps the device matrix a transduced pseudolabel pass ranked (Z of LabelPropagation / TransductiveGMM, Q of BalancedAssignment) so that the
-    prompt steps can train on the ROW behind a pseudolabel instead of its arg-max (engine.soft_ce; off unless installed by soft_targets()).
-    record() is called by pseudolabel_from_features; the steps ask for
-      rows(names)         the matrix row of every file name of a batch (int32 on the matrix's device), -1 for a name that is not in the pool.  Names are
-                          BASE names: the dataset hands those out and the strategies' check_unlabeled is keyed by them; a base name that names two pool
-                          rows raises when it is asked about;
-      col_map(class_ids)  int32 [cz]: the position, in a step's training class list (label ids), of every class the pass ranked -- TRZSL ranks over
-                          the unseen classes and trains over all of them.
-    The store OWNS its buffer: the first record() copies the matrix into it and every later one of the same shape and device overwrites it in place,
-    so the address a captured graph read the matrix from stays valid and the next replay trains on the new pass (steps.GraphedStep).  Another shape
-    allocates another buffer (a graphed step sees its key move and runs eagerly until it is rebuilt).  Multi-rank runs need nothing: every rank
-    ranks the same gathered pool."""
+class _PoolRowStore:
+    """The name / column bookkeeping SoftTargetStore and CandidateStore share: a device buffer `matrix` with one row per pool image that the store OWNS
+    (the first record copies into it, every later one of the same shape, dtype and device overwrites it in place), the pool row of every BASE name and
+    the column map of a training class list."""
+    _dtype, _what, _keyed = torch.float32, "matrix", "soft targets"
 
     def __init__(self):
-        self.matrix = None          # f32 [n, cz] on the device, or None before the first pass
-        self.class_labels = ()      # the label id of every matrix column
+        self.matrix = None          # [n, columns] on the device, or None before the first pass
+        self.class_labels = ()      # the label id of every class the pass ranked
         self.records = 0
         self._row_of = {}           # base name -> pool row, or -2 for a base name that occurs twice
         self._col_maps = {}         # tuple(training label ids) -> int32 [cz] device tensor (one tensor per list: a fixed address, checked once)
 
+    def _columns(self, n_classes):
+        return n_classes
+
     def record(self, paths, class_labels, z):
-        if not torch.is_tensor(z) or z.dim() != 2 or z.dtype != torch.float32 or tuple(z.shape) != (len(paths), len(class_labels)):
-            raise ValueError(f"SoftTargetStore.record: a float32 [{len(paths)}, {len(class_labels)}] matrix was expected, got {getattr(z, 'shape', type(z))} "
-                             f"{getattr(z, 'dtype', None)}")
+        name = str(self._dtype).replace("torch.", "")
+        if not torch.is_tensor(z) or z.dim() != 2 or z.dtype != self._dtype or tuple(z.shape) != (len(paths), self._columns(len(class_labels))):
+            raise ValueError(f"{type(self).__name__}.record: a {name} [{len(paths)}, {self._columns(len(class_labels))}] {self._what} was expected, got "
+                             f"{getattr(z, 'shape', type(z))} {getattr(z, 'dtype', None)}")
         z = z.detach()
         if self.matrix is not None and self.matrix.shape == z.shape and self.matrix.device == z.device:
             self.matrix.copy_(z)
@@ -1120,7 +1116,7 @@ class SoftTargetStore:
         """int32 [len(names)] on the matrix's device.  hard: optional list of flags, True = do not ask about this name (its row is -1: a labelled row
         of the batch, whatever it is called)."""
         if self.matrix is None:
-            raise ValueError("SoftTargetStore.rows: no pass has recorded a matrix yet")
+            raise ValueError(f"{type(self).__name__}.rows: no pass has recorded a {self._what} yet")
         out = []
         for i, n in enumerate(names):
             if hard is not None and hard[i]:
@@ -1128,23 +1124,54 @@ class SoftTargetStore:
                 continue
             r = self._row_of.get(n.split("/")[-1], -1)
             if r == -2:
-                raise ValueError(f"SoftTargetStore: the base name {n.split('/')[-1]!r} names two rows of the pool: soft targets are keyed by base names, "
+                raise ValueError(f"{type(self).__name__}: the base name {n.split('/')[-1]!r} names two rows of the pool: {self._keyed} are keyed by base names, "
                                  "as the strategies' check_unlabeled is")
             out.append(r)
         return torch.tensor(out, dtype=torch.int32).to(self.matrix.device, non_blocking=True)
 
     def col_map(self, class_ids):
         if self.matrix is None:
-            raise ValueError("SoftTargetStore.col_map: no pass has recorded a matrix yet")
+            raise ValueError(f"{type(self).__name__}.col_map: no pass has recorded a {self._what} yet")
         key = tuple(int(c) for c in class_ids)
         if key not in self._col_maps:
             at = {c: i for i, c in enumerate(key)}
             missing = [c for c in self.class_labels if c not in at]
             if missing or len(at) != len(key):
-                raise ValueError(f"SoftTargetStore.col_map: the pass ranked classes {missing} that the training class list {list(key)} does not hold "
+                raise ValueError(f"{type(self).__name__}.col_map: the pass ranked classes {missing} that the training class list {list(key)} does not hold "
                                  "(or that list repeats a class)")
             self._col_maps[key] = torch.tensor([at[c] for c in self.class_labels], dtype=torch.int32, device=self.matrix.device)
         return self._col_maps[key]
+
+
+class SoftTargetStore(_PoolRowStore):
+    """Keeps the device matrix a transduced pseudolabel pass ranked (Z of LabelPropagation / TransductiveGMM, Q of BalancedAssignment) so that the
+    prompt steps can train on the ROW behind a pseudolabel instead of its arg-max (engine.soft_ce; off unless installed by soft_targets()).
+    record() is called by pseudolabel_from_features; the steps ask for
+      rows(names)         the matrix row of every file name of a batch (int32 on the matrix's device), -1 for a name that is not in the pool.  Names are
+                          BASE names: the dataset hands those out and the strategies' check_unlabeled is keyed by them; a base name that names two pool
+                          rows raises when it is asked about;
+      col_map(class_ids)  int32 [cz]: the position, in a step's training class list (label ids), of every class the pass ranked -- TRZSL ranks over
+                          the unseen classes and trains over all of them.
+    The store OWNS its buffer: the first record() copies the matrix into it and every later one of the same shape and device overwrites it in place,
+    so the address a captured graph read the matrix from stays valid and the next replay trains on the new pass (steps.GraphedStep).  Another shape
+    allocates another buffer (a graphed step sees its key move and runs eagerly until it is rebuilt).  Multi-rank runs need nothing: every rank
+    ranks the same gathered pool."""
+
+
+class CandidateStore(_PoolRowStore):
+    """Keeps the candidate SETS of the last pseudolabel pass (engine.candidate_select's mask, int32 [n, ceil(cz / 32)] on the device; `mask` names the
+    buffer) so that the prompt steps can train on the set behind a pseudolabel with the partial-label loss (engine.candidate_ce; off unless installed by
+    candidate_sets()).  SoftTargetStore's contract: it owns its buffer, a later pass of the same shape lands at the same address -- a captured graph
+    trains on the new sets -- rows(names, hard=) gives the mask row of every base name (-1: not in the pool, or a labelled row; a duplicated base name
+    raises when asked about) and col_map(class_ids) the position, in a step's training class list, of every class the pass ranked."""
+    _dtype, _what, _keyed = torch.int32, "mask", "candidate sets"
+
+    def _columns(self, n_classes):
+        return (n_classes + 31) // 32
+
+    @property
+    def mask(self):
+        return self.matrix
 
 
 _SOFT_STORES = []   # stores installed by soft_targets(), innermost last.  Empty unless a caller opened one: no pass records anything by default
@@ -1172,20 +1199,95 @@ def soft_target_store():
     return _SOFT_STORES[-1] if _SOFT_STORES else None
 
 
+class CandidateSelection:
+    """Settings of the candidate-set pseudolabel pass (off unless installed by candidate_sets(); Candidate Pseudolabel Learning, Zhang et al., ICML 2024):
+    every pool image keeps a SET of classes (engine.candidate_select) -- the smallest prefix of its top classes whose running confidence reaches `tau`
+    (intra-instance), joined by `combine` ("intersection", "union", "intra", "inter") with the classes that claim it among their most confident rows of
+    the WHOLE matrix (inter-instance).  slots: how many boards' worth of rows a class claims -- a pass with k pseudo-shots per class uses
+    claim = min(n, slots k), so GRIP's growing k grows the coverage with no schedule of its own.  The defaults are untuned."""
+    infix = "cpl_"      # of the pseudolabel pickle's name, in front of lp_ / gmm_ / ot_...
+
+    def __init__(self, tau=0.99, slots=2, combine="intersection"):
+        self.tau, self.combine = float(tau), combine
+        if not 0.0 < self.tau <= 1.0:
+            raise ValueError(f"CandidateSelection: tau = {tau} (0 < tau <= 1)")
+        if isinstance(slots, bool) or int(slots) != slots or int(slots) < 1:
+            raise ValueError(f"CandidateSelection: slots = {slots!r} (an integer >= 1)")
+        self.slots = int(slots)
+        if combine not in engine.CANDIDATE_COMBINE:
+            raise ValueError(f"CandidateSelection: combine = {combine!r} (one of {sorted(engine.CANDIDATE_COMBINE)})")
+        self.state = None           # (count [n], threshold [cz]) of the most recent pass
+
+    def claim(self, n, k):
+        return n if k == K_ALL else max(1, min(n, self.slots * int(k)))
+
+    def select(self, matrix, paths, class_labels, k, store):
+        """(filepaths, labels) of a pass over `matrix` [n, cz]: every pool row with a non-empty set, in pool order, each once, with the member of highest
+        rank as its (hard) label; the sets go to `store`."""
+        mask, count, label, threshold = engine.candidate_select(matrix, self.claim(matrix.shape[0], k), self.tau, self.combine)
+        store.record(paths, class_labels, mask)
+        self.state = (count, threshold)
+        lab = label.cpu().tolist()
+        keep = [i for i, c in enumerate(lab) if c >= 0]
+        return [paths[i] for i in keep], [class_labels[lab[i]] for i in keep]
+
+    def __repr__(self):
+        return f"CandidateSelection(tau={self.tau}, slots={self.slots}, combine={self.combine!r})"
+
+
+_CANDIDATES = []    # (selection, store) installed by candidate_sets(), innermost last.  Empty unless a caller opened one
+
+
+@contextlib.contextmanager
+def candidate_sets(selection, store):
+    """Install a CandidateSelection and the CandidateStore that receives its sets (or None, None: no-op) for the pseudolabel passes underneath, as
+    label_propagation() and soft_targets() install theirs.  While one is installed pseudolabel_from_features runs the selection instead of the
+    leaderboard scan -- on the matrix it would have ranked: Z / Q of an installed transduction, else the head's probabilities -- the callers that would
+    pick identical_lists take their plain branch, and pseudolabel_top_k names its pickle `..._pseudolabels_cpl_split_...` (`cpl_lp_`, `cpl_gmm_`,
+    `cpl_ot_...` with a transduction) and does not read an existing one (a loaded list has no sets behind it)."""
+    if selection is None and store is None:
+        yield None
+        return
+    if not isinstance(selection, CandidateSelection) or not isinstance(store, CandidateStore):
+        raise TypeError(f"candidate_sets: expected a CandidateSelection and a CandidateStore (or None, None), got {type(selection).__name__} and "
+                        f"{type(store).__name__}")
+    _CANDIDATES.append((selection, store))
+    try:
+        yield store
+    finally:
+        _CANDIDATES.pop()
+
+
+def candidates():
+    """The innermost installed (CandidateSelection, CandidateStore), or None."""
+    return _CANDIDATES[-1] if _CANDIDATES else None
+
+
+def list_infix():
+    """The infix of a pseudolabel pickle's name for what is installed: "", lp_ / gmm_ / ot_..., each with cpl_ in front under candidate_sets()."""
+    return (CandidateSelection.infix if candidates() is not None else "") + (propagation().infix if propagation() is not None else "")
+
+
 @torch.no_grad()
 def pseudolabel_from_features(img_emb, txt_emb, scale, paths, class_labels, k, argmax_on="probs"):
     """Head + scan.  argmax_on: "probs" (compute_pseudo_labels, :39) or "logits" (assign_pseudo_labels).  With a LabelPropagation or a
     TransductiveGMM installed the scan runs on its Z over the whole (gathered, on every rank alike) pool and on arg-max Z, for both forms of argmax_on;
-    a SoftTargetStore installed by soft_targets() then records that matrix."""
+    a SoftTargetStore installed by soft_targets() then records that matrix.  With candidate_sets() installed the selection replaces the scan (on Z / Q,
+    else on the head's probabilities): the lists are the pool rows with a non-empty candidate set, each once, in pool order."""
     logits, probs, am_l, am_p = engine.cosine_head(img_emb, txt_emb, scale)
     lp = propagation()
+    cand = candidates()
     if lp is not None and img_emb.shape[0] >= 2:        # (a pool of one image has no neighbour to hear from)
         z, z_pred = lp.transduce(img_emb, probs, paths)
         store = soft_target_store()
         if store is not None:
             store.record(paths, class_labels, z)
+        if cand is not None:
+            return cand[0].select(z, paths, class_labels, k, cand[1])
         return leaderboard(z.cpu().numpy(), z_pred.cpu().numpy(), paths, class_labels, k)
     if soft_target_store() is not None:
         soft_target_store().forget()        # a pass without a transduction has no matrix: the rows of an earlier one no longer name its lists
+    if cand is not None:
+        return cand[0].select(probs, paths, class_labels, k, cand[1])
     pred = (am_p if argmax_on == "probs" else am_l).cpu().numpy()
     return leaderboard(probs.cpu().numpy(), pred, paths, class_labels, k)

@@ -9,7 +9,7 @@ import torch
 
 from . import dist as gdist
 from . import engine
-from .engine import CosineHeadFn, SoftCEFn, WeightedCEFn
+from .engine import CandidateCEFn, CosineHeadFn, SoftCEFn, WeightedCEFn
 
 
 def fpl_row_weights(is_pseudo, gamma_seen=1.0, gamma_pseudo=1.0):
@@ -50,10 +50,39 @@ class SoftTargets:
         return (None if m is None else (m.data_ptr(), tuple(m.shape), c.data_ptr()), self.temperature, self.smoothing)
 
 
+class CandidateTargets:
+    """What a prompt step needs to train on candidate SETS with the partial-label loss (engine.candidate_ce): `mask` int32 [rows, ceil(cz / 32)] on the
+    device -- the sets the last pseudolabel pass selected, read in place (pseudolabels.CandidateStore.mask) -- and `col_map` int32 [cz], the logits
+    column of every mask column.  A step takes it as `soft=`, as it takes a SoftTargets, together with a per-batch `soft_row` int32 [B] that then carries
+    the MASK row of each batch row (-1: a hard row); step_loss dispatches on the type.  tip_step and adapter_step keep hard labels."""
+
+    def __init__(self, mask, col_map):
+        if not torch.is_tensor(mask) or mask.dim() != 2 or mask.dtype != torch.int32 or not torch.is_tensor(col_map) or col_map.dim() != 1:
+            raise ValueError(f"CandidateTargets: an int32 [rows, words] mask and a [cz] col_map were expected, got {getattr(mask, 'shape', type(mask))} "
+                             f"{getattr(mask, 'dtype', None)} and {getattr(col_map, 'shape', type(col_map))}")
+        if mask.shape[1] != (col_map.shape[0] + 31) // 32:
+            raise ValueError(f"CandidateTargets: a mask of {mask.shape[1]} words for {col_map.shape[0]} classes (ceil(cz / 32) words)")
+        self.mask, self.col_map = mask, col_map
+
+    @property
+    def matrix(self):
+        """The per-pool-row buffer, under the name the graphed steps ask a SoftTargets for."""
+        return self.mask
+
+    def key(self):
+        """What a captured graph depends on: the addresses it read the mask and the map from, and their shapes."""
+        return ("candidates", self.mask.data_ptr(), tuple(self.mask.shape), self.col_map.data_ptr())
+
+
 def step_loss(logits, labels, row_weight, soft=None, soft_row=None):
-    """The loss of a prompt step: WeightedCEFn, exactly as before, without `soft`; SoftCEFn on the rows of soft.matrix that soft_row names with it."""
+    """The loss of a prompt step: WeightedCEFn, exactly as before, without `soft`; SoftCEFn on the rows of soft.matrix that soft_row names with a
+    SoftTargets; CandidateCEFn on the rows of soft.mask that soft_row names with a CandidateTargets."""
     if soft is None:
         return WeightedCEFn.apply(logits, labels, row_weight)
+    if isinstance(soft, CandidateTargets):
+        if soft_row is None:
+            raise ValueError("a step with candidate sets needs the batch's soft_row (the mask row of every batch row, -1 for a hard row)")
+        return CandidateCEFn.apply(logits, labels, row_weight, soft.mask, soft_row, soft.col_map)
     if soft.matrix is None:
         return SoftCEFn.apply(logits, labels, row_weight, None, None, None, soft.temperature, soft.smoothing)
     if soft_row is None:

@@ -77,7 +77,9 @@ def compute_pseudo_labels(k, template, dataset, classnames, transform, clip_mode
     log.info(f"Compute {k} pseudo-labeles")
     if pl.propagation() is not None:
         log.info(f"{pl.propagation()} is installed: the pass propagates over the pool and takes the plain branch (no reference list to be identical to)")
-    if pl.mode() == "identical" and pl.propagation() is None and not getattr(clip_model, "exact", False) and hasattr(clip_model, "exact_twin"):
+    if pl.candidates() is not None:
+        log.info(f"{pl.candidates()[0]} is installed: the pass selects candidate sets and takes the plain branch (no reference list to be identical to)")
+    if pl.mode() == "identical" and pl.propagation() is None and pl.candidates() is None and not getattr(clip_model, "exact", False) and hasattr(clip_model, "exact_twin"):
         # the fp32 scan's lists at close to f16 throughput: f16 screen, exact re-encode of the undecidable rows only
         twin = clip_model.exact_twin()
         with torch.no_grad():
@@ -105,11 +107,13 @@ def compute_pseudo_labels(k, template, dataset, classnames, transform, clip_mode
 def pseudolabel_top_k(config, data_name, k, template, dataset, classnames, transform, clip_model, label_to_idx, device,
                       vis_encoder, split_seed):
     # a propagated list ("lp_"), a GMM list ("gmm_"), a balanced one ("ot_", "ot_lp_", "ot_gmm_") and a reference-style one never share a cache file
-    lp = pl.propagation().infix if pl.propagation() is not None else ""
+    # ("cpl_" in front of any of them for candidate sets)
+    lp = pl.list_infix()
     filename = f"pseudolabels/{data_name}_{vis_encoder.replace('/', '')}_{config.LEARNING_PARADIGM}_{config.MODEL}_{k}_pseudolabels_{lp}split_{split_seed}.pickle"
     # while a SoftTargetStore is installed (pl.soft_targets) an existing file is not read: a loaded list has no matrix behind it -- the pass runs and
     # rewrites the same file (same name, same schema)
-    if os.path.exists(filename) and pl.soft_target_store() is None:
+    # (the same while a CandidateStore is installed by pl.candidate_sets: a loaded list has no sets behind it)
+    if os.path.exists(filename) and pl.soft_target_store() is None and pl.candidates() is None:
         with open(filename, "rb") as f:
             pseudolabels = pickle.load(f)
         dataset.filepaths = pseudolabels["filepaths"]
