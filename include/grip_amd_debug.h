@@ -143,6 +143,11 @@ int grip_debug_patch_gather(const void* images, int images_f16, void* out, int o
 int grip_debug_transpose(const void* in, void* out, int f32, int rows, int cols, int ld_in, void* stream);
 /* out[b] = x[b * row_stride + (row_index ? row_index[b] : 0)], rows of width d: f16 elements (d % 8 == 0), or four_byte != 0: 4-byte elements (d % 4 == 0). */
 int grip_debug_gather_rows(const void* x, const int32_t* row_index, int row_stride, void* out, int n_rows, int d, int four_byte, void* stream);
+/* The UPT mixer's workspace by name (csrc/mixer.hip carve_mixer, tests/test_gpu_mixer_kernels.py): buffer `index` of the carve-up for S = 2 + n_deep tokens --
+ * its name (a string constant of the library), its offset in floats from the 256-byte-aligned base of the workspace and its used length in floats
+ * (without the padding to 64 floats).  Non-zero past the end and for every shape the mixer refuses.  Host only: nothing is launched. */
+int grip_debug_upt_mixer_slot(int n_prompt, int n_deep, int text_width, int vision_width, int dim, int index, const char** name, int64_t* offset_floats,
+                              int64_t* floats);
 
 /* GEMM launch profiler: while enabled, every 4th GEMM launch is bracketed by HIP events on its stream. */
 int grip_profile_enable(int on);

@@ -11,6 +11,8 @@
 // Deep UPT (vpt_embeddings_deep in the sequence, S = 2 + n_deep tokens) has its own row-tiled Linear and attention kernels: see "deep UPT" below.
 #include "common.h"
 
+#include <vector>
+
 namespace {
 enum Pro { PRO_NONE = 0, PRO_LN = 1, PRO_ATTN = 2, PRO_LNBWD_ADD = 3, PRO_ATTNBWD = 4 };
 enum Epi { MEPI_NONE = 0, MEPI_GELU = 1, MEPI_RESID = 2, MEPI_RESID_F16 = 3, MEPI_F16ROUND = 4, MEPI_GELUGRAD = 5 };
@@ -365,20 +367,28 @@ struct MixWs {
     float *pm, *dsm, *xv, *dv_all;
     size_t floats;
 };
-MixWs carve_mixer(float* base, int P, int dt, int dv, int D, int S = 2) {
+struct MixSlot { const char* name; size_t off, n; };
+MixWs carve_mixer(float* base, int P, int dt, int dv, int D, int S = 2, std::vector<MixSlot>* slots = nullptr) {
     MixWs w{};
     const size_t R = (size_t)S * P;
     size_t off = 0;
-    auto take = [&](size_t n) { float* p = base ? base + off : nullptr; off += (n + 63) / 64 * 64; return p; };
-    w.x0 = take(R * D); w.st1 = take(R * 2); w.y1 = take(R * D); w.qkv = take(R * 3 * D); w.o = take(R * D); w.x1 = take(R * D);
-    w.st2 = take(R * 2); w.z = take(R * D); w.h = take(R * 4 * D); w.g = take(R * 4 * D); w.x2 = take(R * D); w.out16 = take(R * D);
-    w.d_x2 = take(R * D); w.dh = take(R * 4 * D); w.dz = take(R * D); w.d_x1 = take(R * D); w.d_o = take(R * D); w.dqkv = take(R * 3 * D);
-    w.dy = take(R * D); w.d_x0 = take(R * D);
-    w.T_cq = take((size_t)dt * D); w.T_vq = take((size_t)dv * D); w.T_pr = take((size_t)4 * D * D); w.T_fc = take((size_t)4 * D * D);
-    w.T_o = take((size_t)D * D); w.T_in = take((size_t)3 * D * D); w.T_cp = take((size_t)dt * D); w.T_vp = take((size_t)dv * D);
+    auto take = [&](const char* name, size_t n) {
+        float* p = base ? base + off : nullptr;
+        if (slots) slots->push_back(MixSlot{name, off, n});
+        off += (n + 63) / 64 * 64;
+        return p;
+    };
+    w.x0 = take("x0", R * D); w.st1 = take("st1", R * 2); w.y1 = take("y1", R * D); w.qkv = take("qkv", R * 3 * D); w.o = take("o", R * D);
+    w.x1 = take("x1", R * D); w.st2 = take("st2", R * 2); w.z = take("z", R * D); w.h = take("h", R * 4 * D); w.g = take("g", R * 4 * D);
+    w.x2 = take("x2", R * D); w.out16 = take("out16", R * D);
+    w.d_x2 = take("d_x2", R * D); w.dh = take("dh", R * 4 * D); w.dz = take("dz", R * D); w.d_x1 = take("d_x1", R * D); w.d_o = take("d_o", R * D);
+    w.dqkv = take("dqkv", R * 3 * D); w.dy = take("dy", R * D); w.d_x0 = take("d_x0", R * D);
+    w.T_cq = take("T_cq", (size_t)dt * D); w.T_vq = take("T_vq", (size_t)dv * D); w.T_pr = take("T_pr", (size_t)4 * D * D);
+    w.T_fc = take("T_fc", (size_t)4 * D * D); w.T_o = take("T_o", (size_t)D * D); w.T_in = take("T_in", (size_t)3 * D * D);
+    w.T_cp = take("T_cp", (size_t)dt * D); w.T_vp = take("T_vp", (size_t)dv * D);
     if (S > 2) {
         const size_t Rv = (size_t)(S - 1) * P;
-        w.pm = take((size_t)P * S * S); w.dsm = take((size_t)P * S * S); w.xv = take(Rv * dv); w.dv_all = take(Rv * dv);
+        w.pm = take("pm", (size_t)P * S * S); w.dsm = take("dsm", (size_t)P * S * S); w.xv = take("xv", Rv * dv); w.dv_all = take("dv_all", Rv * dv);
     }
     w.floats = off;
     return w;
@@ -702,4 +712,23 @@ extern "C" int grip_upt_mixer_backward_deep(const grip_upt_mixer* m, const float
         GRIP_CHECK_HIP(hipGetLastError());
         return GRIP_OK;
     } catch (...) { grip_set_error("upt_mixer_backward_deep: exception"); return GRIP_ERR_ARG; }
+}
+
+// ---- test hook (include/grip_amd_debug.h): the workspace carve-up by name, host only ------------------------------------------------------------
+extern "C" int grip_debug_upt_mixer_slot(int n_prompt, int n_deep, int text_width, int vision_width, int dim, int index, const char** name,
+                                         int64_t* offset_floats, int64_t* floats) {
+    try {
+        GRIP_REQUIRE(name && offset_floats && floats, "debug_upt_mixer_slot: null pointer");
+        GRIP_REQUIRE(n_deep >= 0 && n_deep <= MIX_MAX_DEEP, "debug_upt_mixer_slot: n_deep = %d out of range (0 .. %d deep visual prompts)", n_deep, MIX_MAX_DEEP);
+        grip_upt_mixer m{};
+        m.n_prompt = n_prompt; m.text_width = text_width; m.vision_width = vision_width; m.dim = dim;
+        RUNM(check_shape(&m));
+        std::vector<MixSlot> slots;
+        carve_mixer(nullptr, n_prompt, text_width, vision_width, dim, 2 + n_deep, &slots);
+        GRIP_REQUIRE(index >= 0 && index < (int)slots.size(), "debug_upt_mixer_slot: slot %d past the end (%d)", index, (int)slots.size());
+        *name = slots[(size_t)index].name;
+        *offset_floats = (int64_t)slots[(size_t)index].off;
+        *floats = (int64_t)slots[(size_t)index].n;
+        return GRIP_OK;
+    } catch (...) { grip_set_error("debug_upt_mixer_slot: exception"); return GRIP_ERR_ARG; }
 }

@@ -200,6 +200,8 @@ _DEBUG_SIGS = {          # kernel-level test hooks (csrc/tower.hip), not part of
     "grip_debug_patch_gather": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "grip_debug_transpose": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "grip_debug_gather_rows": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    # the UPT mixer's workspace carve-up by name (csrc/mixer.hip), host only
+    "grip_debug_upt_mixer_slot": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(ctypes.c_char_p), POINTER(c_int64), POINTER(c_int64)]),
 }
 
 _lib = None
