@@ -586,6 +586,36 @@ int grip_candidate_ce(const float* logits, const int32_t* labels, const float* r
                       const int32_t* cand_row, const int32_t* col_map, float* loss, float* grad_logits, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 9 additions) Multi-view mode of an image's view embeddings (pseudolabels.MultiView; csrc/view_mode.hip).  After MTA (Zanella & Ben Ayed, "On the
+ * test-time zero-shot generalization of vision-language models: Do we really need prompt learning?", CVPR 2024): training-free, a robust mean-shift over
+ * the V views of an image with per-view inlier weights.  What follows is THE MODEL OF THIS HEADER, NOT THE PAPER'S CODE (no gradient steps on y, no
+ * stopping rule, fixed counts, the bandwidth rule below).
+ * Image i has V view embeddings f_p [e] and, optionally, the views' class probabilities s_p [c]; view 0 is the un-augmented image.
+ *   1. u_p = f_p / |f_p|,  G = U U^T,  d2_pq = max(0, 2 - 2 G_pq).
+ *   2. r = max(1, floor(rho (V - 1))) (the product in double on the f32 rho); h2_p = the mean of the r smallest d2_pq over q != p, added in ascending
+ *      (value, index) order in plain f32 and divided by r; then h2_p = max(h2_p, h2_floor).
+ *   3. A = S S^T [V, V], diagonal included (view_probs == NULL: the affinity term is off).
+ *   4. m = mode_in (NULL: u_0),  y = y_in (NULL: 1 / V).
+ *   5. `outer` times:
+ *        k_p = exp(-sum_d (u_pd - m_d)^2 / (2 h2_p))                               (the direct form, not the expanded one)
+ *        `inner` times:  y = softmax_p((k_p + lam sum_q A_pq y_q) / lam_y)         (q ascending; the maximum is subtracted first)
+ *        m_d = sum_p y_p k_p u_pd / max(sum_p y_p k_p, 2^-126)                      (p ascending)
+ *   6. mode_out = m (NOT normalised: the heads normalise their input), y_out = y, h2_out = h2 (may be NULL).  outer = 0: the start state and h2.
+ *   view_emb [n, v, e], view_probs [n, v, c] or NULL, mode_in / mode_out [n, e], y_in / y_out / h2_out [n, v]; all f32, element offsets 64-bit.
+ *   2 <= v <= 64; e a multiple of 64 up to 1 024; any c >= 1, any n >= 1; 0 < rho <= 1; lam >= 0, lam_y > 0, h2_floor > 0, all finite; outer, inner >= 0.
+ *   view_emb, mode_in and mode_out 16-byte aligned.  mode_in may BE mode_out and y_in may BE y_out; no other aliasing.  A view of zero norm, or a norm
+ *   whose square leaves the f32 range, is the caller's duty.
+ * ONE launch per call (one workgroup per image; both [V, V] products on the f32-input MFMA, exact f32; V padded to 16-row tiles with zero rows that take
+ * no part in the selection, the softmax or the sums), no atomics, no scratch, every reduction in a fixed order: two calls are bit-equal, and an image's
+ * output bits depend on its own operands only -- not on n, not on its place in the launch.  The kernel keeps its state in the LDS: the workspace is
+ * 0 bytes today (grip_view_mode_workspace says so; `workspace` may then be NULL) and the call needs no device.  Out-of-range arguments are refused with
+ * nothing written.  This kernel is not where a multi-view pass spends its time: the V tower forwards per image are. */
+int grip_view_mode_workspace(int n, int v, int c, int e, size_t* bytes);
+int grip_view_mode(const float* view_emb, const float* view_probs, int n, int v, int c, int e, float rho, float lam, float lam_y, float h2_floor, int outer,
+                   int inner, const float* mode_in, const float* y_in, float* mode_out, float* y_out, float* h2_out, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CLIP preprocessing of one decoded image: the `_transform` the reference applies per item on the host
  * (data/dataset.py:64-79 via clip.load's preprocess): Resize(n_px, BICUBIC) -> CenterCrop(n_px) -> ToTensor -> Normalize.
  * Bit-exact with Pillow's 8-bit bicubic resample; only the cropped rows / columns are produced.

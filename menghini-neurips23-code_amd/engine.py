@@ -1352,6 +1352,50 @@ def sinkhorn_balance(probs, tau=1.0, iters=3, prior=None, log_scale=None):
     return q, pred, mass, b_out
 
 
+VIEW_MODE_MAX_VIEWS = 64        # csrc/view_mode.hip: VM_MAXV
+VIEW_MODE_MAX_E = 1024          # csrc/view_mode.hip: VM_MAXE
+VIEW_MODE_DEFAULTS = dict(rho=0.3, lam=4.0, lam_y=0.2, h2_floor=2.0 ** -20, outer=5, inner=3)      # rho, lam, lam_y: the paper's; the counts are untuned
+
+
+def view_mode(view_emb, view_probs=None, rho=0.3, lam=4.0, lam_y=0.2, h2_floor=2.0 ** -20, outer=5, inner=3, mode_in=None, y_in=None, want_h2=False):
+    """(mode f32 [n, e], y f32 [n, v][, h2 f32 [n, v]]): the multi-view mode of include/grip_amd.h on the native kernel (csrc/view_mode.hip) -- view_emb
+    [n, v, e] f32 (view 0 the un-augmented image), view_probs [n, v, c] f32 or None (no affinity term), mode_in [n, e] / y_in [n, v] or None (u_0 and
+    1 / v).  mode is not normalised.  Everything is validated here, on the host, before the one launch; bit-identical from call to call, and an image's
+    bits do not depend on n or on its place."""
+    if not torch.is_tensor(view_emb) or view_emb.dim() != 3 or view_emb.dtype != torch.float32:
+        raise native.GripError(f"view_mode: view_emb must be a float32 [n, v, e] tensor, got {getattr(view_emb, 'shape', type(view_emb))} "
+                               f"{getattr(view_emb, 'dtype', None)}")
+    n, v, e = view_emb.shape
+    require_gpu(view_emb.device)
+    if n < 1 or not 2 <= v <= VIEW_MODE_MAX_VIEWS or e < 64 or e > VIEW_MODE_MAX_E or e % 64:
+        raise native.GripError(f"view_mode: n = {n}, v = {v}, e = {e} (n >= 1, 2 <= v <= {VIEW_MODE_MAX_VIEWS}, e a multiple of 64 up to {VIEW_MODE_MAX_E})")
+    f = view_emb.detach().contiguous()
+    c, s = 1, None
+    if view_probs is not None:
+        if not torch.is_tensor(view_probs) or view_probs.dim() != 3 or tuple(view_probs.shape[:2]) != (n, v) or view_probs.shape[2] < 1:
+            raise native.GripError(f"view_mode: view_probs must be a float32 [{n}, {v}, c] tensor, got {getattr(view_probs, 'shape', type(view_probs))}")
+        c = view_probs.shape[2]
+        s = _gmm_operand("view_mode", "view_probs", view_probs, (n, v, c), f)
+    m0 = None if mode_in is None else _gmm_operand("view_mode", "mode_in", mode_in, (n, e), f)
+    y0 = None if y_in is None else _gmm_operand("view_mode", "y_in", y_in, (n, v), f)
+    for name, val, ok in (("rho", rho, lambda x: 0 < x <= 1), ("lam", lam, lambda x: x >= 0), ("lam_y", lam_y, lambda x: x > 0),
+                          ("h2_floor", h2_floor, lambda x: x > 0)):
+        x = float(val)
+        if not (math.isfinite(x) and ok(x)):
+            raise native.GripError(f"view_mode: {name} = {x:g} is out of range (0 < rho <= 1, lam >= 0, lam_y > 0, h2_floor > 0, all finite)")
+    for name, val in (("outer", outer), ("inner", inner)):
+        if isinstance(val, bool) or not isinstance(val, int) or val < 0:
+            raise native.GripError(f"view_mode: {name} = {val!r} (an integer >= 0)")
+    lib = native.lib()
+    ws = _gda_workspace(lib.grip_view_mode_workspace, (n, v, c, e), f.device)      # (0 bytes today: the kernel keeps its state in the LDS)
+    mode = torch.empty(n, e, dtype=torch.float32, device=f.device)
+    y = torch.empty(n, v, dtype=torch.float32, device=f.device)
+    h2 = torch.empty(n, v, dtype=torch.float32, device=f.device) if want_h2 else None
+    native.check(lib.grip_view_mode(_ptr(f), _ptr(s), n, v, c, e, float(rho), float(lam), float(lam_y), float(h2_floor), outer, inner, _ptr(m0), _ptr(y0),
+                                    _ptr(mode), _ptr(y), _ptr(h2), _ptr(ws) if ws.numel() else c_void_p(0), ws.numel(), _stream()))
+    return (mode, y, h2) if want_h2 else (mode, y)
+
+
 def leaderboard_scan(probs, pred, path_rank, k):
     """Host scan (exact, sequential).  probs [n,c] f32 CPU, pred [n] int32 CPU, path_rank [n] int64 CPU."""
     import numpy as np

@@ -25,6 +25,16 @@ from ..utils import pseudolabel_top_k
 log = logging.getLogger(__name__)
 
 
+def multi_view_from_config(config, keep=False):
+    """The pl.MultiView of a config's MV_* settings (MV_VIEWS outside 2 .. 64 and bad boxes or parameters raise ValueError); keep: a frozen image tower,
+    whose view embeddings may stay across passes up to MV_CACHE_BYTES (default 4 GiB)."""
+    g = lambda name, default: getattr(config, name, default)
+    return pl.MultiView(views=g("MV_VIEWS", 16), scale=tuple(g("MV_SCALE", (0.5, 1.0))), ratio=tuple(g("MV_RATIO", (3.0 / 4.0, 4.0 / 3.0))),
+                        flip=float(g("MV_FLIP", 0.5)), seed=int(g("MV_SEED", 0)), rho=float(g("MV_RHO", 0.3)), lam=float(g("MV_LAMBDA", 4.0)),
+                        lam_y=float(g("MV_LAMBDA_Y", 0.2)), outer=int(g("MV_OUTER", 5)), inner=int(g("MV_INNER", 3)),
+                        keep_bytes=int(g("MV_CACHE_BYTES", 4 << 30)) if keep else 0)
+
+
 def make_scheduler(optimizer, config):
     """WarmupCosineSchedule stepped once per EPOCH (utils/schedulers.py:36-65 of the reference)."""
     warm, total = int(getattr(config, "WARMUP_EPOCHS", 0)), int(config.EPOCHS)
@@ -137,6 +147,17 @@ class TrainingStrategy:
             self.candidate_selection = pl.CandidateSelection(tau=float(getattr(config, "CPL_TAU", 0.99)), slots=getattr(config, "CPL_SLOTS", 2),
                                                              combine=getattr(config, "CPL_COMBINE", "intersection"))
             self.candidate_store = pl.CandidateStore()
+        # MULTIVIEW_PSEUDOLABELS (all modalities and paradigms, default False; MV_VIEWS 16, MV_SCALE (0.5, 1.0), MV_RATIO (3/4, 4/3), MV_FLIP 0.5,
+        # MV_SEED 0, MV_RHO 0.3, MV_LAMBDA 4, MV_LAMBDA_Y 0.2: the paper's; MV_OUTER 5, MV_INNER 3: untuned): every pseudolabel pass encodes MV_VIEWS views
+        # of every pool image under the current prompts and hands the mean-shift mode of their embeddings (pl.MultiView -> engine.view_mode) to the head,
+        # the transductions, the balance, the soft rows and the candidate sets in place of the single embedding.  V tower forwards per image.  A textual
+        # strategy (frozen tower) keeps a pool's view embeddings across iterations when they fit MV_CACHE_BYTES (default 4 GiB); the others encode every
+        # pass.  MV_PREDICT (default False): `predict`, and so validation and test, classify the mode of each item's views; adapter, Tip, GDA and probe
+        # terms then apply to the mode.  The training sets of those heads stay single-view.
+        self.multi_view, self.mv_predict = None, bool(getattr(config, "MV_PREDICT", False))
+        if bool(getattr(config, "MULTIVIEW_PSEUDOLABELS", False)) or self.mv_predict:
+            self.multi_view = multi_view_from_config(config, keep=self.modality == "text")
+        self.mv_passes = self.multi_view if bool(getattr(config, "MULTIVIEW_PSEUDOLABELS", False)) else None      # what the passes install
         self.declare_custom_encoder()
         self.initialize_prompts_parameters()
 
@@ -366,7 +387,7 @@ class TrainingStrategy:
         pseudo_classes = self.classes if self.paradigm in ("ssl", "ul") else self.unseen_classes
         # the frozen-CLIP pass runs the same towers over the same pool as the trained-prompt passes after it
         with pl.pool_cache(self.pool_cache), pl.label_propagation(self.transduction()), pl.soft_targets(self.soft_store), \
-                pl.candidate_sets(self.candidate_selection, self.candidate_store):
+                pl.candidate_sets(self.candidate_selection, self.candidate_store), pl.multi_view(self.mv_passes):
             pseudolabel_top_k(c, c.DATASET_NAME, int(c.N_PSEUDOSHOTS), self.template, unlabeled_data, pseudo_classes, self.transform,
                               self.clip_model, self.label_to_idx, self.device, c.VIS_ENCODER, getattr(c, "SPLIT_SEED", 0))
         return self.merge_pseudolabels(train_data, unlabeled_data)
@@ -576,7 +597,13 @@ class TrainingStrategy:
         outs = []
         for batch in self._loader(data, False):
             img = batch[0].to(self.device)
-            image_features, text_features = self.features(img, classes)
+            if self.mv_predict:       # MV_PREDICT: the mode of each item's views under the current model stands in for its single embedding
+                views = self.multi_view.make_views(img.float().contiguous(), list(batch[-1]))      # (the item names: last in a batch, with or without labels)
+                view_features, text_features = self.features(views, classes)
+                image_features = self.multi_view.aggregate(view_features.detach().float().view(img.shape[0], self.multi_view.views, -1), text_features.detach(),
+                                                           self.scale())
+            else:
+                image_features, text_features = self.features(img, classes)
             if self.adapter is not None:      # CLIP_ADAPTER: the features are adapted before the head (row by row: the batching changes no bit)
                 image_features = self.adapter(image_features)
             logits, _, am, _ = cosine_head(image_features, text_features, self.scale(), want_probs=False)
@@ -917,18 +944,34 @@ class TrainingStrategy:
         multimodal_fpl.py:223 runs BOTH towers and the mixer for every image).  paths: the pool's ordered paths, the key under which a textual
         strategy's pool cache (installed by the caller) holds the prompt-free embeddings."""
         tower = self.clip_model.visual.tower
+        mv = pl.multiview()
+
+        def pool(txt, prefix=None, deep=None):
+            """With a MultiView installed: the modes of every image's views under the current visual prompts in place of encode_pool's rows (they depend
+            on txt: the pool cache is neither read nor written)."""
+            if paths is None:
+                raise ValueError("trained_features: a MultiView is installed and needs the pool's ordered paths (they name the views' boxes)")
+            return mv.features(tower, images, paths, txt, self.scale(), chunk=chunk, prefix=prefix, deep=deep), txt
         if self.modality == "text":
             self.model.classes = classes
+            if mv is not None:
+                return pool(self.model(classes))
             return pl.encode_pool(tower, images, chunk=chunk, paths=paths), self.model(classes)
         if self.modality == "image":
+            if mv is not None:
+                return pool(self.fixed_text_features(classes), self.model.prefix.detach(), self.deep_prompts())
             return pl.encode_pool(tower, images, chunk=chunk, prefix=self.model.prefix.detach(), deep=self.deep_prompts()), self.fixed_text_features(classes)
         self.model.classes = classes
         if self.maple():
             ctx, deep_text, vis_prefix, vis_deep = self.model.couple()
             txt = self.model.text_encoder(ctx, classes, **({} if deep_text is None else {"deep_prompts": deep_text}))
+            if mv is not None:
+                return pool(txt, vis_prefix.detach(), None if vis_deep is None else vis_deep.detach())
             return pl.encode_pool(tower, images, chunk=chunk, prefix=vis_prefix.detach(), deep=None if vis_deep is None else vis_deep.detach()), txt
         coop_embs, vpt_embs, *deep = self.model.mix()
         txt = self.model.text_encoder(coop_embs, classes)
+        if mv is not None:
+            return pool(txt, vpt_embs.detach(), deep[0].detach() if deep else None)
         return pl.encode_pool(tower, images, chunk=chunk, prefix=vpt_embs.detach(), deep=deep[0].detach() if deep else None), txt
 
     @torch.no_grad()
@@ -941,12 +984,14 @@ class TrainingStrategy:
         labels = [self.label_to_idx[c] for c in classes]
         paths = list(unlabeled_data.filepaths)      # the pool as passed to the pass (grip_train resets it to the original list every iteration): the cache's key
         with pl.pool_cache(self.pool_cache), pl.label_propagation(self.transduction()), pl.soft_targets(self.soft_store), \
-                pl.candidate_sets(self.candidate_selection, self.candidate_store):       # (None: nothing is installed)
+                pl.candidate_sets(self.candidate_selection, self.candidate_store), pl.multi_view(self.mv_passes):       # (None: nothing is installed)
             if pl.propagation() is not None:
                 log.info(f"{pl.propagation()} is installed: the pass propagates over the pool and takes the plain branch (no reference list to be identical to)")
             if pl.candidates() is not None:
                 log.info(f"{pl.candidates()[0]} is installed: the pass selects candidate sets and takes the plain branch (no reference list to be identical to)")
-            if pl.mode() == "identical" and pl.propagation() is None and pl.candidates() is None and not self.clip_model.exact:
+            if pl.multiview() is not None:
+                log.info(f"{pl.multiview()} is installed: the pass encodes every image's views and takes the plain branch (no reference list to be identical to)")
+            if pl.mode() == "identical" and pl.propagation() is None and pl.candidates() is None and pl.multiview() is None and not self.clip_model.exact:
                 # the lists the reference's fp32 pass would produce with these prompts: f16 screen + exact refinement
                 twin = self.clip_model.exact_twin()
                 txt, vprompt = self.trained_text_features(classes, twin)

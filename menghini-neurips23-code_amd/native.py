@@ -131,6 +131,10 @@ _SIGS = {
     "grip_candidate_select_workspace": (c_int, [c_int, c_int, POINTER(c_size_t)]),
     "grip_candidate_select": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "grip_candidate_ce": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # (ABI 9 additions) multi-view mode: inlier-weighted mean-shift over an image's view embeddings (csrc/view_mode.hip)
+    "grip_view_mode_workspace": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "grip_view_mode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "grip_preprocess_image": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                       c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "grip_preprocess_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

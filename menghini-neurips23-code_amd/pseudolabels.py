@@ -9,6 +9,7 @@ go through the tower in chunks instead of one by one.
 """
 import contextlib
 import logging
+import math
 import os
 import weakref
 
@@ -1263,9 +1264,133 @@ def candidates():
     return _CANDIDATES[-1] if _CANDIDATES else None
 
 
+class MultiView:
+    """Settings of the multi-view pseudolabel pass (off unless installed by multi_view(); after MTA, Zanella & Ben Ayed, CVPR 2024 -- the model of
+    include/grip_amd.h, not the paper's code): every pool image is encoded `views` times -- view 0 the image as it is, views 1 .. V - 1 boxes of an
+    augment.ViewSampler(seed, scale, ratio, flip) under the image's base name with the EPOCH FIXED AT 0, so a pool's views are the same in every pass
+    and on every rank -- and the feature row the pass hands on is the inlier-weighted mean-shift mode of the image's view embeddings
+    (engine.view_mode; the affinity of two views is the dot product of their class probabilities under the pass's text features).  The result is one
+    [n, e] matrix, not normalised, that pseudolabel_from_features and everything behind it consume unchanged.  The cost is V tower forwards per image.
+    rho, lam, lam_y are the paper's values; outer, inner and h2_floor are untuned.
+    keep_bytes > 0 (textual strategies: the image tower is frozen): the [n, V, e] view embeddings of a pool are kept, keyed by its ordered paths, when
+    they fit, and the next pass over the same pool encodes nothing.  `encodes` counts the pools actually encoded."""
+    infix = "mv_"       # of the pseudolabel pickle's name, between cpl_ and lp_ / gmm_ / ot_...
+
+    def __init__(self, views=16, scale=(0.5, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip=0.5, seed=0, rho=0.3, lam=4.0, lam_y=0.2, h2_floor=2.0 ** -20,
+                 outer=5, inner=3, keep_bytes=0):
+        from .augment import ViewSampler
+        if isinstance(views, bool) or not isinstance(views, int) or not 2 <= views <= engine.VIEW_MODE_MAX_VIEWS:
+            raise ValueError(f"MultiView: views = {views!r} (an integer in 2 .. {engine.VIEW_MODE_MAX_VIEWS})")
+        self.views = views
+        self.sampler = ViewSampler(seed=seed, scale=scale, ratio=ratio, flip=flip)       # (raises on a bad scale / ratio / flip)
+        self.rho, self.lam, self.lam_y, self.h2_floor = float(rho), float(lam), float(lam_y), float(h2_floor)
+        if not (0.0 < self.rho <= 1.0 and 0.0 <= self.lam < math.inf and 0.0 < self.lam_y < math.inf and 0.0 < self.h2_floor < math.inf):
+            raise ValueError(f"MultiView: rho = {rho}, lam = {lam}, lam_y = {lam_y}, h2_floor = {h2_floor} (0 < rho <= 1, lam >= 0, lam_y > 0, "
+                             f"h2_floor > 0, all finite)")
+        for name, val in (("outer", outer), ("inner", inner)):
+            if isinstance(val, bool) or not isinstance(val, int) or val < 0:
+                raise ValueError(f"MultiView: {name} = {val!r} (an integer >= 0)")
+        self.outer, self.inner = outer, inner
+        self.keep_bytes = int(keep_bytes)
+        self._kept = None       # (tuple(paths), tower, [n, V, e]) of the most recent pool that fitted
+        self.encodes = 0
+        self.last_y = None      # [n, V] view weights of the most recent aggregate (diagnostics)
+
+    def boxes(self, names, H, W):
+        """int32 [len(names) * V, 5] of (top, left, height, width, flip), image-major: view 0 of every image is the whole image, un-flipped; view p >= 1
+        is the sampler's box of (seed, base name, epoch 0, view p)."""
+        out = np.empty((len(names), self.views, 5), dtype=np.int32)
+        out[:, 0] = (0, 0, H, W, 0)
+        for i, name in enumerate(names):
+            base = os.path.basename(str(name))
+            for p in range(1, self.views):
+                out[i, p] = self.sampler.box(base, 0, H, W, view=p)
+        return out.reshape(-1, 5)
+
+    def make_views(self, images, names):
+        """images [B, 3, H, H] f32 on the GPU -> their views [B * V, 3, H, H], image-major (view 0 is a bit-exact copy)."""
+        from . import augment
+        B, _, H, W = images.shape
+        return augment.views(images, self.boxes(names, H, W), rows=np.repeat(np.arange(B, dtype=np.int64), self.views), n_px=H)
+
+    @torch.no_grad()
+    def encode_views(self, tower, images, paths, chunk=880, prefix=None, deep=None):
+        """[n, V, e] f32: the view embeddings of an ordered pool (`images` as encode_pool takes it), max(1, chunk // V) images at a time, so a chunk of
+        views is no larger than a chunk of images is today.  Every chunk of views goes through encode_pool WITHOUT a cache key (a view is not the pool
+        image the PoolFeatureCache knows); what encode_pool does under torch.distributed is inherited."""
+        n = images.shape[0] if torch.is_tensor(images) else images.n
+        if len(paths) != n:
+            raise ValueError(f"{len(paths)} paths for a pool of {n} images")
+        key = tuple(paths)
+        if prefix is None and deep is None and self._kept is not None and self._kept[0] == key and self._kept[1] is tower:
+            return self._kept[2]
+        V, dev = self.views, tower.device
+        out = torch.empty(n, V, tower.embed_dim, dtype=torch.float32, device=dev)
+        step = max(1, int(chunk) // V)
+        per_image = engine.is_per_image_prefix(prefix)
+        if hasattr(images, "plan"):
+            images.plan(0, n, step)
+        for lo in range(0, n, step):
+            hi = min(n, lo + step)
+            x = (images[lo:hi] if torch.is_tensor(images) else images(lo, hi)).to(dev, torch.float32).contiguous()
+            vw = self.make_views(x, paths[lo:hi])
+            pf = prefix[lo:hi].repeat_interleave(V, dim=0) if per_image else prefix
+            out[lo:hi] = encode_pool(tower, vw, chunk=chunk, prefix=pf, deep=deep).view(hi - lo, V, -1)
+        self.encodes += 1
+        if prefix is None and deep is None and 0 < _nbytes(out) <= self.keep_bytes:
+            self._kept = (key, tower, out)
+        return out
+
+    @torch.no_grad()
+    def aggregate(self, view_emb, txt, scale):
+        """[n, e] modes of the [n, V, e] view embeddings: engine.cosine_head on the n V rows for the views' class probabilities, then engine.view_mode."""
+        n, V, e = view_emb.shape
+        _, probs, _, _ = engine.cosine_head(view_emb.reshape(n * V, e), txt, scale)
+        mode, self.last_y = engine.view_mode(view_emb, probs.view(n, V, -1), rho=self.rho, lam=self.lam, lam_y=self.lam_y, h2_floor=self.h2_floor,
+                                             outer=self.outer, inner=self.inner)
+        return mode
+
+    def features(self, tower, images, paths, txt, scale, chunk=880, prefix=None, deep=None):
+        """encode_views + aggregate: what a pass hands to pseudolabel_from_features in place of encode_pool's rows."""
+        return self.aggregate(self.encode_views(tower, images, paths, chunk=chunk, prefix=prefix, deep=deep), txt, scale)
+
+    def __repr__(self):
+        return (f"MultiView(views={self.views}, scale={self.sampler.scale}, ratio={self.sampler.ratio}, flip={self.sampler.flip}, seed={self.sampler.seed}, "
+                f"rho={self.rho}, lam={self.lam}, lam_y={self.lam_y}, outer={self.outer}, inner={self.inner})")
+
+
+_MULTIVIEW = []     # settings installed by multi_view(), innermost last.  Empty unless a caller opened one: every pass sees each pool image once by default
+
+
+@contextlib.contextmanager
+def multi_view(mv):
+    """Install `mv` (a MultiView, or None: no-op) for the pseudolabel passes underneath, as label_propagation() / soft_targets() / candidate_sets()
+    install theirs.  While one is installed compute_pseudo_labels and Strategy.trained_features hand the modes of the pool's views to
+    pseudolabel_from_features instead of encode_pool's rows, the callers that would pick identical_lists take their plain branch (no reference list can
+    be identical to a multi-view one), the PoolFeatureCache is neither read nor written for modes (they depend on the text features) and
+    pseudolabel_top_k names its pickle `..._pseudolabels_mv_split_...` (`cpl_mv_lp_`, ... with the other switches)."""
+    if mv is None:
+        yield None
+        return
+    if not isinstance(mv, MultiView):
+        raise TypeError(f"multi_view: expected a MultiView or None, got {type(mv).__name__}")
+    _MULTIVIEW.append(mv)
+    try:
+        yield mv
+    finally:
+        _MULTIVIEW.pop()
+
+
+def multiview():
+    """The innermost installed MultiView, or None."""
+    return _MULTIVIEW[-1] if _MULTIVIEW else None
+
+
 def list_infix():
-    """The infix of a pseudolabel pickle's name for what is installed: "", lp_ / gmm_ / ot_..., each with cpl_ in front under candidate_sets()."""
-    return (CandidateSelection.infix if candidates() is not None else "") + (propagation().infix if propagation() is not None else "")
+    """The infix of a pseudolabel pickle's name for what is installed: "", lp_ / gmm_ / ot_..., with mv_ in front under multi_view() and cpl_ in front
+    of both under candidate_sets()."""
+    return ((CandidateSelection.infix if candidates() is not None else "") + (MultiView.infix if multiview() is not None else "") +
+            (propagation().infix if propagation() is not None else ""))
 
 
 @torch.no_grad()

@@ -79,7 +79,9 @@ def compute_pseudo_labels(k, template, dataset, classnames, transform, clip_mode
         log.info(f"{pl.propagation()} is installed: the pass propagates over the pool and takes the plain branch (no reference list to be identical to)")
     if pl.candidates() is not None:
         log.info(f"{pl.candidates()[0]} is installed: the pass selects candidate sets and takes the plain branch (no reference list to be identical to)")
-    if pl.mode() == "identical" and pl.propagation() is None and pl.candidates() is None and not getattr(clip_model, "exact", False) and hasattr(clip_model, "exact_twin"):
+    if pl.multiview() is not None:
+        log.info(f"{pl.multiview()} is installed: the pass encodes every image's views and takes the plain branch (no reference list to be identical to)")
+    if pl.mode() == "identical" and pl.propagation() is None and pl.candidates() is None and pl.multiview() is None and not getattr(clip_model, "exact", False) and hasattr(clip_model, "exact_twin"):
         # the fp32 scan's lists at close to f16 throughput: f16 screen, exact re-encode of the undecidable rows only
         twin = clip_model.exact_twin()
         with torch.no_grad():
@@ -92,7 +94,10 @@ def compute_pseudo_labels(k, template, dataset, classnames, transform, clip_mode
     else:
         with torch.no_grad():
             txt = clip_model.encode_text(text)                                 # once, not once per image
-            emb = pl.encode_pool(clip_model.visual.tower, images, chunk=chunk, paths=list(dataset.filepaths))     # (the paths key a cache installed by pl.pool_cache)
+            if pl.multiview() is not None:      # the modes of every image's views: they depend on txt, so the pool cache neither reads nor writes them
+                emb = pl.multiview().features(clip_model.visual.tower, images, list(dataset.filepaths), txt, scale, chunk=chunk)
+            else:
+                emb = pl.encode_pool(clip_model.visual.tower, images, chunk=chunk, paths=list(dataset.filepaths))     # (the paths key a cache installed by pl.pool_cache)
         new_imgs, new_labels = pl.pseudolabel_from_features(emb, txt, scale, list(dataset.filepaths), class_labels, k, argmax_on="probs")
     dataset.filepaths = new_imgs
     dataset.labels = new_labels
@@ -107,7 +112,7 @@ def compute_pseudo_labels(k, template, dataset, classnames, transform, clip_mode
 def pseudolabel_top_k(config, data_name, k, template, dataset, classnames, transform, clip_model, label_to_idx, device,
                       vis_encoder, split_seed):
     # a propagated list ("lp_"), a GMM list ("gmm_"), a balanced one ("ot_", "ot_lp_", "ot_gmm_") and a reference-style one never share a cache file
-    # ("cpl_" in front of any of them for candidate sets)
+    # ("cpl_" in front of any of them for candidate sets, "mv_" after it for multi-view modes)
     lp = pl.list_infix()
     filename = f"pseudolabels/{data_name}_{vis_encoder.replace('/', '')}_{config.LEARNING_PARADIGM}_{config.MODEL}_{k}_pseudolabels_{lp}split_{split_seed}.pickle"
     # while a SoftTargetStore is installed (pl.soft_targets) an existing file is not read: a loaded list has no matrix behind it -- the pass runs and
