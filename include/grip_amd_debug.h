@@ -149,6 +149,21 @@ int grip_debug_gather_rows(const void* x, const int32_t* row_index, int row_stri
 int grip_debug_upt_mixer_slot(int n_prompt, int n_deep, int text_width, int vision_width, int dim, int index, const char** name, int64_t* offset_floats,
                               int64_t* floats);
 
+/* The workspace of a tower pass by name (csrc/tower.hip carve, tests/test_gpu_tower_passes.py): buffer `index` of the carve-up grip_vit_forward /
+ * grip_text_forward and their backwards use for (batch, n_prefix, seq_len, train, shared = the shared-prefix row layout) -- its name (a string constant of
+ * the library), its layer (-1: not a per-layer buffer), its offset in bytes from the workspace base and the bytes the passes use of it (without the padding
+ * to 256).  Recorded by the carve itself.  An alias is reported at the offset of the buffer it lies on ("patches" on "h").  Non-zero past the end and for
+ * everything the carve refuses.  Host only: nothing is launched.  Weights: grip_layout_slot. */
+int grip_debug_tower_slot(const struct grip_tower* tower, int batch, int n_prefix, int seq_len, int train, int shared, int index, const char** name, int* layer,
+                          int64_t* offset_bytes, int64_t* bytes);
+/* Launch budget of the NEXT tower pass of the calling host thread (grip_vit_forward*, grip_text_forward*, grip_*_backward_*): the pass issues its first n kernel
+ * launches, then returns GRIP_ERR_LAUNCH_BUDGET between two launches; grip_last_error() reads "launch budget: stopped after <n> launches, before <the call
+ * that would have come next>".  n <= 0: off (the default).  The budget switches itself off when it trips and when a pass returns, so n >= the launches of
+ * the pass lets it finish.  Only kernel launches count.  A forward stopped early registers no pending state; a backward stopped early has consumed its
+ * forward.  While off, a launch costs one comparison of a thread-local host integer, and a pass two stores to it. */
+#define GRIP_ERR_LAUNCH_BUDGET 64
+int grip_debug_launch_budget(int64_t n);
+
 /* GEMM launch profiler: while enabled, every 4th GEMM launch is bracketed by HIP events on its stream. */
 int grip_profile_enable(int on);
 /* Per slot (variant * 16 + epilogue id) in [0, n): launches sampled, their total milliseconds and total 2*M*N*K. */

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "common.h"
+#include "../../include/grip_amd_debug.h"      // the hooks defined here are checked against their declarations
 
 // ---------------------------------------------------------------------------------------------- errors
 static thread_local char g_err[512] = "";
@@ -167,7 +168,9 @@ extern "C" int grip_layout_size(const grip_dims* dims, int64_t* n_f16, int64_t* 
 // ---------------------------------------------------------------------------------------------- handle
 // Activation buffers are declared half_t* but hold f32 elements in exact mode (element size `es` below); the forward passes
 // them on as untyped pointers + the f32 flag, and the backward (f16 towers only) uses them as declared.
+struct CarveRec { const char* name; int layer; size_t offset, bytes; };      // one buffer of a carve-up, as carve() handed it out (grip_debug_tower_slot)
 struct Workspace {  // carve of the caller's buffer for one (batch, n_prefix, train) problem
+    std::vector<CarveRec>* rec = nullptr;      // set by grip_debug_tower_slot alone: carve() notes every buffer here
     int batch = 0, P = 0, train = 0, S = 0, M = 0;
     int64_t Mp = 0;
     resid_t* x = nullptr;      // inference residual stream
@@ -289,73 +292,83 @@ static int carve(const grip_tower* t, int batch, int P, int train, char* base, W
     w.Mp = round_up64(w.M, 256);
     const int64_t Bp = round_up64(batch, 256);
     size_t off = 0;
-    auto take = [&](size_t nbytes) { char* p = base ? base + off : nullptr; off += (nbytes + 255) / 256 * 256; return (void*)p; };
-    if (!train) w.x = (resid_t*)take(w.Mp * d * es);
-    if (!train && !t->f32) w.x_lo = (half_t*)take(w.Mp * d * 2);      // lo parts of a compensated stream (GRIP_FWD_STREAM_HILO)
-    w.xn = (half_t*)take(w.Mp * d * es);
-    if (!train) { w.qkv = (half_t*)take(w.Mp * 3 * d * es); w.att = (half_t*)take(w.Mp * d * es); }
-    w.h = (half_t*)take(w.Mp * 4 * d * es);
-    w.cls16 = (half_t*)take(Bp * d * es);
+    // every buffer is handed out by name: grip_debug_tower_slot (w.rec set) reports exactly what the passes get
+    auto take = [&](const char* name, size_t nbytes, int layer = -1) {
+        char* p = base ? base + off : nullptr;
+        if (w.rec) w.rec->push_back({name, layer, off, nbytes});
+        off += (nbytes + 255) / 256 * 256;
+        return (void*)p;
+    };
+    if (!train) w.x = (resid_t*)take("x", w.Mp * d * es);
+    if (!train && !t->f32) w.x_lo = (half_t*)take("x_lo", w.Mp * d * 2);      // lo parts of a compensated stream (GRIP_FWD_STREAM_HILO)
+    w.xn = (half_t*)take("xn", w.Mp * d * es);
+    if (!train) { w.qkv = (half_t*)take("qkv", w.Mp * 3 * d * es); w.att = (half_t*)take("att", w.Mp * d * es); }
+    const size_t h_off = off;
+    w.h = (half_t*)take("h", w.Mp * 4 * d * es);
+    w.cls16 = (half_t*)take("cls16", Bp * d * es);
     w.rows_last = train && !t->f32 && !shared && !last_block_full();
     if (!train || w.rows_last) {       // compact [batch, .] buffers of a last block that runs for the read rows only (f32 / split towers: 4-byte elements)
-        w.row_x = (half_t*)take(Bp * d * es);
-        if (!train && !t->f32) w.row_x_lo = (half_t*)take(Bp * d * 2);
-        w.row_att = (half_t*)take(Bp * d * es);
-        w.row_xn = (half_t*)take(Bp * d * es);
-        w.row_h = (half_t*)take(Bp * 4 * d * es);
+        w.row_x = (half_t*)take("row_x", Bp * d * es);
+        if (!train && !t->f32) w.row_x_lo = (half_t*)take("row_x_lo", Bp * d * 2);
+        w.row_att = (half_t*)take("row_att", Bp * d * es);
+        w.row_xn = (half_t*)take("row_xn", Bp * d * es);
+        w.row_h = (half_t*)take("row_h", Bp * 4 * d * es);
     }
     if (w.rows_last) {
-        w.row_hpre = (half_t*)take(Bp * 4 * d * 2);
-        w.row_xmid = (resid_t*)take(Bp * d * sizeof(resid_t));
-        w.row_xout = (resid_t*)take(Bp * d * sizeof(resid_t));
-        w.drow = (float*)take(Bp * d * 4);
-        w.drow_h = (half_t*)take(Bp * d * 2);
-        w.row_dh = (half_t*)take(Bp * 4 * d * 2);
+        w.row_hpre = (half_t*)take("row_hpre", Bp * 4 * d * 2);
+        w.row_xmid = (resid_t*)take("row_xmid", Bp * d * sizeof(resid_t));
+        w.row_xout = (resid_t*)take("row_xout", Bp * d * sizeof(resid_t));
+        w.drow = (float*)take("drow", Bp * d * 4);
+        w.drow_h = (half_t*)take("drow_h", Bp * d * 2);
+        w.row_dh = (half_t*)take("row_dh", Bp * 4 * d * 2);
         w.ks_row = gemm_pick_ksplit(batch, d, 4 * d);
-        w.row_dln = (float*)take(Bp * d * 4 * (size_t)w.ks_row);
-        w.row_datt = (half_t*)take(Bp * d * 2);
+        w.row_dln = (float*)take("row_dln", Bp * d * 4 * (size_t)w.ks_row);
+        w.row_datt = (half_t*)take("row_datt", Bp * d * 2);
     }
     if (!t->f32) {
-        w.stat_part = (float*)take(w.Mp * (d / 64) * 2 * sizeof(float));
-        w.rowstat = (float*)take(w.Mp * 2 * sizeof(float));
+        w.stat_part = (float*)take("stat_part", w.Mp * (d / 64) * 2 * sizeof(float));
+        w.rowstat = (float*)take("rowstat", w.Mp * 2 * sizeof(float));
     }
     if (D.kind == 0) {
         const int64_t G2 = D.seq0 - 1;
         const int64_t prow = round_up64(batch * G2, 256);
-        w.patches = prow * t->L.kpad <= w.Mp * 4 * d ? w.h : (half_t*)take(prow * t->L.kpad * es);   // alias of h when it fits
-        w.patch_out = (float*)take(batch * G2 * d * 4);
+        if (prow * t->L.kpad <= w.Mp * 4 * d) {      // alias of h when it fits: recorded at h's offset
+            w.patches = w.h;
+            if (w.rec) w.rec->push_back({"patches", -1, h_off, (size_t)(prow * t->L.kpad) * es});
+        } else w.patches = (half_t*)take("patches", prow * t->L.kpad * es);
+        w.patch_out = (float*)take("patch_out", batch * G2 * d * 4);
     }
     if (train) {
         const int Lc = D.layers;
         w.x_in.assign((size_t)Lc + 1, nullptr); w.x_mid.assign((size_t)Lc, nullptr);
         w.qkv_l.assign((size_t)Lc, nullptr); w.att_l.assign((size_t)Lc, nullptr); w.hpre_l.assign((size_t)Lc, nullptr);
-        for (int i = 0; i <= Lc; ++i) w.x_in[(size_t)i] = (resid_t*)take(w.Mp * d * sizeof(resid_t));
+        for (int i = 0; i <= Lc; ++i) w.x_in[(size_t)i] = (resid_t*)take("x_in", w.Mp * d * sizeof(resid_t), i);
         for (int i = 0; i < Lc; ++i) {
-            w.x_mid[(size_t)i] = (resid_t*)take(w.Mp * d * sizeof(resid_t));
-            w.qkv_l[(size_t)i] = (half_t*)take(w.Mp * 3 * d * 2);
-            w.att_l[(size_t)i] = (half_t*)take(w.Mp * d * 2);
-            w.hpre_l[(size_t)i] = (half_t*)take(w.Mp * 4 * d * 2);
+            w.x_mid[(size_t)i] = (resid_t*)take("x_mid", w.Mp * d * sizeof(resid_t), i);
+            w.qkv_l[(size_t)i] = (half_t*)take("qkv_l", w.Mp * 3 * d * 2, i);
+            w.att_l[(size_t)i] = (half_t*)take("att_l", w.Mp * d * 2, i);
+            w.hpre_l[(size_t)i] = (half_t*)take("hpre_l", w.Mp * 4 * d * 2, i);
         }
-        w.dx = (float*)take(w.Mp * d * 4);
+        w.dx = (float*)take("dx", w.Mp * d * 4);
         // split-K partial buffers of the two EPI_F32 input-gradient GEMMs of a block (summed by ln_bwd_add)
         w.ks_fc = gemm_pick_ksplit((int)w.M, d, 4 * d);
         w.ks_in = gemm_pick_ksplit((int)w.M, d, 3 * d);
-        w.dln = (float*)take(w.Mp * d * 4 * (size_t)(w.ks_fc > w.ks_in ? w.ks_fc : w.ks_in));
-        w.dxh = (half_t*)take(w.Mp * d * 2);
-        w.dh = (half_t*)take(w.Mp * 4 * d * 2);
-        w.dqkv = (half_t*)take(w.Mp * 3 * d * 2);
-        w.datt = (half_t*)take(w.Mp * d * 2);
-        w.dcls = (float*)take(Bp * d * 4);
-        w.gemb16 = (half_t*)take(Bp * D.embed_dim * 2);
-        w.scale = (float*)take(256);
-        if (w.Ps) w.kv_part = (float*)take((size_t)batch * w.Ps * 2 * d * 4);
+        w.dln = (float*)take("dln", w.Mp * d * 4 * (size_t)(w.ks_fc > w.ks_in ? w.ks_fc : w.ks_in));
+        w.dxh = (half_t*)take("dxh", w.Mp * d * 2);
+        w.dh = (half_t*)take("dh", w.Mp * 4 * d * 2);
+        w.dqkv = (half_t*)take("dqkv", w.Mp * 3 * d * 2);
+        w.datt = (half_t*)take("datt", w.Mp * d * 2);
+        w.dcls = (float*)take("dcls", Bp * d * 4);
+        w.gemb16 = (half_t*)take("gemb16", Bp * D.embed_dim * 2);
+        w.scale = (float*)take("scale", 2 * sizeof(float));
+        if (w.Ps) w.kv_part = (float*)take("kv_part", (size_t)batch * w.Ps * 2 * d * 4);
         if (D.kind == 1 && !t->f32) {      // text tower, f16
             w.coop_ks = gemm_pick_coop_split((int)w.M, d, 4 * d);
             if (w.coop_ks > 1) {
                 const size_t tiles = (size_t)((w.M + 63) / 64) * (size_t)(d / 128);
-                w.coop_scratch = (float*)take(tiles * (size_t)w.coop_ks * 4 * 2048 * sizeof(float));
+                w.coop_scratch = (float*)take("coop_scratch", tiles * (size_t)w.coop_ks * 4 * 2048 * sizeof(float));
                 w.coop_cnt_bytes = tiles * 4 * sizeof(int);
-                w.coop_cnt = (int*)take(w.coop_cnt_bytes);
+                w.coop_cnt = (int*)take("coop_cnt", w.coop_cnt_bytes);
             }
         }
     }
@@ -458,8 +471,48 @@ extern "C" int grip_workspace_bytes(const grip_tower* t, int batch, int n_prefix
     } catch (...) { grip_set_error("workspace_bytes: exception"); return GRIP_ERR_ARG; }
 }
 
+// The carve-up by name (include/grip_amd_debug.h): carve() itself, run without a base pointer, notes every buffer it hands out.
+extern "C" int grip_debug_tower_slot(const grip_tower* t, int batch, int n_prefix, int seq_len, int train, int shared, int index, const char** name, int* layer,
+                                     int64_t* offset_bytes, int64_t* bytes) {
+    GRIP_REQUIRE(t && name && layer && offset_bytes && bytes, "debug_tower_slot: null pointer");
+    try {
+        std::vector<CarveRec> rec;
+        Workspace w;
+        w.rec = &rec;
+        int rc = carve(t, batch, n_prefix, train, nullptr, w, seq_len, shared);
+        if (rc) return rc;
+        GRIP_REQUIRE(index >= 0 && index < (int)rec.size(), "debug_tower_slot: slot %d past the end (%d)", index, (int)rec.size());
+        const CarveRec& r = rec[(size_t)index];
+        *name = r.name; *layer = r.layer; *offset_bytes = (int64_t)r.offset; *bytes = (int64_t)r.bytes;
+        return GRIP_OK;
+    } catch (...) { grip_set_error("debug_tower_slot: exception"); return GRIP_ERR_ARG; }
+}
+
 // ---------------------------------------------------------------------------------------------- forward
 #define RUN(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
+
+// Launch budget (grip_debug_launch_budget, include/grip_amd_debug.h): a test may let a tower pass issue its first n kernel launches only, to look at the
+// workspace between two launches.  Off (0) unless a test sets it: every launch site then costs one comparison of a host integer.  The budget ends a pass
+// BETWEEN launches and switches itself off when it trips or when the pass returns (PassScope), whatever the pass returns.  Per host thread, like the
+// error text: a budget set on one thread governs the next pass of that thread alone, and passes on other threads neither see nor cancel it.
+static thread_local int64_t g_launch_budget = 0;     // 0 = off, else launches the current pass may still issue + 1
+static thread_local int64_t g_launch_count = 0;      // launches the current pass has issued under a budget
+static bool launch_budget_spent(const char* what) {
+    if (--g_launch_budget > 0) { ++g_launch_count; return false; }
+    g_launch_budget = 0;
+    grip_set_error("launch budget: stopped after %lld launches, before %s", (long long)g_launch_count, what);
+    return true;
+}
+struct PassScope {      // a tower pass begins and ends: no budget outlives it
+    PassScope() { g_launch_count = 0; }
+    ~PassScope() { g_launch_budget = 0; }
+};
+#define LAUNCH(expr) do { if (g_launch_budget && launch_budget_spent(#expr)) return GRIP_ERR_LAUNCH_BUDGET; RUN(expr); } while (0)
+extern "C" int grip_debug_launch_budget(int64_t n) {
+    g_launch_budget = n > 0 ? n + 1 : 0;
+    g_launch_count = 0;
+    return GRIP_OK;
+}
 
 // One tower pass over the residual stream.  f16 towers never run a stand-alone LayerNorm inside the blocks: the statistics of
 // every row travel with the stream -- the assembly / embedding kernel writes (mean, rstd) of x0, each residual GEMM epilogue
@@ -500,10 +553,10 @@ static int run_blocks(grip_tower* t, Workspace& w, resid_t* x0, int causal, cons
         const bool last = l + 1 == t->D.layers;
         if (l >= 1 && l <= w.n_deep) {    // deep prompts: the block's input rows 1 .. P := deep[l - 1] before anything reads x (train: x_in[l], what the backward differentiates)
             if (t->D.kind == 0)
-                RUN(launch_vit_deep_insert(w.deep + (size_t)(l - 1) * w.P * d, x, f, hilo ? w.x_lo : nullptr, parts_in ? w.stat_part : nullptr,
+                LAUNCH(launch_vit_deep_insert(w.deep + (size_t)(l - 1) * w.P * d, x, f, hilo ? w.x_lo : nullptr, parts_in ? w.stat_part : nullptr,
                                            (fold && !parts_in) ? w.rowstat : nullptr, w.batch, w.S, w.P, (int)w.M, d, s));
             else      // text tower: either row layout, one context for every class or one per class
-                RUN(launch_text_deep_insert(w.deep + (size_t)(l - 1) * w.deep_classes * w.P * d, w.deep_classes, x, f, parts_in ? w.stat_part : nullptr,
+                LAUNCH(launch_text_deep_insert(w.deep + (size_t)(l - 1) * w.deep_classes * w.P * d, w.deep_classes, x, f, parts_in ? w.stat_part : nullptr,
                                             (fold && !parts_in) ? w.rowstat : nullptr, w.batch, w.S, w.P, w.Ps, (int)w.M, d, s));
         }
         if (last && rows_only) {
@@ -511,27 +564,27 @@ static int run_blocks(grip_tower* t, Workspace& w, resid_t* x0, int causal, cons
             GemmArgs a{};
             a.A = x; a.W = t->w16 + lw.in_wG + (int64_t)d * d; a.M = w.M; a.m_pad = w.Mp; a.N = 2 * d; a.K = d; a.bias = F + lw.in_bb + d; a.colsum = F + lw.in_cs + d;
             a.rowstat = w.rowstat; a.out = w.qkv + d; a.ldc = 3 * d;
-            RUN(launch_gemm(EPI_LNFOLD_F16, a, s));
-            RUN(launch_gather_rows(x, read_rows, w.S, w.row_x, w.batch, d, s));
-            if (hilo) RUN(launch_gather_rows(w.x_lo, read_rows, w.S, w.row_x_lo, w.batch, d, s));      // the read rows keep their compensation through the block's two adds
-            RUN(launch_layernorm_f16(w.row_x, F + lw.ln1_g, F + lw.ln1_b, w.row_xn, 0, w.batch, d, s));
+            LAUNCH(launch_gemm(EPI_LNFOLD_F16, a, s));
+            LAUNCH(launch_gather_rows(x, read_rows, w.S, w.row_x, w.batch, d, s));
+            if (hilo) LAUNCH(launch_gather_rows(w.x_lo, read_rows, w.S, w.row_x_lo, w.batch, d, s));      // the read rows keep their compensation through the block's two adds
+            LAUNCH(launch_layernorm_f16(w.row_x, F + lw.ln1_g, F + lw.ln1_b, w.row_xn, 0, w.batch, d, s));
             a = GemmArgs{};
             a.A = w.row_xn; a.W = t->w16 + lw.in_w; a.M = w.batch; a.m_pad = round_up64(w.batch, 256); a.N = d; a.K = d; a.bias = F + lw.in_b; a.out = w.row_h; a.ldc = d;
-            RUN(launch_gemm(EPI_BIAS_F16, a, s));
-            RUN(launch_attention_row(w.qkv, w.row_h, read_rows, w.row_att, w.batch, w.S, H, causal, s));
+            LAUNCH(launch_gemm(EPI_BIAS_F16, a, s));
+            LAUNCH(launch_attention_row(w.qkv, w.row_h, read_rows, w.row_att, w.batch, w.S, H, causal, s));
             const int64_t Bp = round_up64(w.batch, 256);
             a = GemmArgs{};
             a.A = w.row_att; a.W = t->w16 + lw.out_w; a.M = w.batch; a.m_pad = Bp; a.N = d; a.K = d; a.bias = F + lw.out_b; a.resid = w.row_x; a.out = w.row_x; a.ldc = d;
             if (hilo) { a.resid_lo = w.row_x_lo; a.stat_part = w.stat_part; }      // (the compensated form lives in the statistics-carrying epilogue; nobody reads these sums)
-            RUN(launch_gemm(EPI_BIAS_RESID, a, s));
-            RUN(launch_layernorm_f16(w.row_x, F + lw.ln2_g, F + lw.ln2_b, w.row_xn, 0, w.batch, d, s));
+            LAUNCH(launch_gemm(EPI_BIAS_RESID, a, s));
+            LAUNCH(launch_layernorm_f16(w.row_x, F + lw.ln2_g, F + lw.ln2_b, w.row_xn, 0, w.batch, d, s));
             a = GemmArgs{};
             a.A = w.row_xn; a.W = t->w16 + lw.fc_w; a.M = w.batch; a.m_pad = Bp; a.N = 4 * d; a.K = d; a.bias = F + lw.fc_b; a.out = w.row_h; a.ldc = 4 * d;
-            RUN(launch_gemm(EPI_BIAS_GELU_F16, a, s));
+            LAUNCH(launch_gemm(EPI_BIAS_GELU_F16, a, s));
             a = GemmArgs{};
             a.A = w.row_h; a.W = t->w16 + lw.proj_w; a.M = w.batch; a.m_pad = Bp; a.N = d; a.K = 4 * d; a.bias = F + lw.proj_b; a.resid = w.row_x; a.out = w.row_x; a.ldc = d;
             if (hilo) { a.resid_lo = w.row_x_lo; a.stat_part = w.stat_part; }
-            RUN(launch_gemm(EPI_BIAS_RESID, a, s));
+            LAUNCH(launch_gemm(EPI_BIAS_RESID, a, s));
             x = w.row_x;
             *compact = true;
             break;
@@ -544,27 +597,27 @@ static int run_blocks(grip_tower* t, Workspace& w, resid_t* x0, int causal, cons
             const char* in_w = (const char*)t->wop(t->split ? lw.in_wS : lw.in_w);
             float* qkv32 = (float*)(void*)w.qkv;
             GemmArgs a{};
-            RUN(launch_layernorm_f16(x, F + lw.ln1_g, F + lw.ln1_b, w.xn, gf, w.M, d, s));
+            LAUNCH(launch_layernorm_f16(x, F + lw.ln1_g, F + lw.ln1_b, w.xn, gf, w.M, d, s));
             a.f32 = gf; a.w_exact = t->w_exact; a.A = w.xn; a.W = in_w + wb; a.M = w.M; a.m_pad = w.Mp; a.N = 2 * d; a.K = d; a.bias = F + lw.in_b + d; a.out = qkv32 + d; a.ldc = 3 * d;
-            RUN(launch_gemm(EPI_BIAS_F16, a, s));
-            RUN(launch_gather_rows4(x, read_rows, w.S, w.row_x, w.batch, d, s));
-            RUN(launch_gather_rows4(w.xn, read_rows, w.S, w.row_xn, w.batch, d, s));
+            LAUNCH(launch_gemm(EPI_BIAS_F16, a, s));
+            LAUNCH(launch_gather_rows4(x, read_rows, w.S, w.row_x, w.batch, d, s));
+            LAUNCH(launch_gather_rows4(w.xn, read_rows, w.S, w.row_xn, w.batch, d, s));
             a = GemmArgs{};
             a.f32 = gf; a.w_exact = t->w_exact; a.A = w.row_xn; a.W = in_w; a.M = w.batch; a.m_pad = Bp; a.N = d; a.K = d; a.bias = F + lw.in_b; a.out = w.row_h; a.ldc = d;
-            RUN(launch_gemm(EPI_BIAS_F16, a, s));
-            RUN(launch_attention_row_f32(qkv32, (const float*)(const void*)w.row_h, read_rows, (float*)(void*)w.row_att, w.batch, w.S, H, causal, s, t->split));
+            LAUNCH(launch_gemm(EPI_BIAS_F16, a, s));
+            LAUNCH(launch_attention_row_f32(qkv32, (const float*)(const void*)w.row_h, read_rows, (float*)(void*)w.row_att, w.batch, w.S, H, causal, s, t->split));
             a = GemmArgs{};
             a.f32 = gf; a.w_exact = t->w_exact; a.A = w.row_att; a.W = t->wop(t->split ? lw.out_wS : lw.out_w); a.M = w.batch; a.m_pad = Bp; a.N = d; a.K = d; a.bias = F + lw.out_b;
             a.resid = w.row_x; a.out = w.row_x; a.ldc = d;
-            RUN(launch_gemm(EPI_BIAS_RESID, a, s));
-            RUN(launch_layernorm_f16(w.row_x, F + lw.ln2_g, F + lw.ln2_b, w.row_xn, gf, w.batch, d, s));
+            LAUNCH(launch_gemm(EPI_BIAS_RESID, a, s));
+            LAUNCH(launch_layernorm_f16(w.row_x, F + lw.ln2_g, F + lw.ln2_b, w.row_xn, gf, w.batch, d, s));
             a = GemmArgs{};
             a.f32 = gf; a.w_exact = t->w_exact; a.A = w.row_xn; a.W = t->wop(t->split ? lw.fc_wS : lw.fc_w); a.M = w.batch; a.m_pad = Bp; a.N = 4 * d; a.K = d; a.bias = F + lw.fc_b; a.out = w.row_h; a.ldc = 4 * d;
-            RUN(launch_gemm(EPI_BIAS_GELU_F16, a, s));
+            LAUNCH(launch_gemm(EPI_BIAS_GELU_F16, a, s));
             a = GemmArgs{};
             a.f32 = gf; a.w_exact = t->w_exact; a.A = w.row_h; a.W = t->wop(t->split ? lw.proj_wS : lw.proj_w); a.M = w.batch; a.m_pad = Bp; a.N = d; a.K = 4 * d; a.bias = F + lw.proj_b;
             a.resid = w.row_x; a.out = w.row_x; a.ldc = d;
-            RUN(launch_gemm(EPI_BIAS_RESID, a, s));
+            LAUNCH(launch_gemm(EPI_BIAS_RESID, a, s));
             x = w.row_x;
             *compact = true;
             break;
@@ -576,22 +629,22 @@ static int run_blocks(grip_tower* t, Workspace& w, resid_t* x0, int causal, cons
             const int64_t Bp = round_up64(w.batch, 256);
             half_t* qkv = w.qkv_l[(size_t)l];
             GemmArgs a{};
-            RUN(launch_layernorm_f16(x, F + lw.ln1_g, F + lw.ln1_b, w.xn, 0, w.M, d, s));
+            LAUNCH(launch_layernorm_f16(x, F + lw.ln1_g, F + lw.ln1_b, w.xn, 0, w.M, d, s));
             a.rot_rows = 1;
             a.A = w.xn; a.W = t->w16 + lw.in_w; a.M = w.M; a.m_pad = w.Mp; a.N = 3 * d; a.K = d; a.bias = F + lw.in_b; a.out = qkv; a.ldc = 3 * d;
-            RUN(launch_gemm(EPI_BIAS_F16, a, s));
-            RUN(launch_attention_row(qkv, nullptr, read_rows, w.row_att, w.batch, w.S, H, causal, s, /*train=*/1));
-            RUN(launch_gather_rows(x, read_rows, w.S, w.row_x, w.batch, d, s));
+            LAUNCH(launch_gemm(EPI_BIAS_F16, a, s));
+            LAUNCH(launch_attention_row(qkv, nullptr, read_rows, w.row_att, w.batch, w.S, H, causal, s, /*train=*/1));
+            LAUNCH(launch_gather_rows(x, read_rows, w.S, w.row_x, w.batch, d, s));
             a = GemmArgs{};
             a.A = w.row_att; a.W = t->w16 + lw.out_w; a.M = w.batch; a.m_pad = Bp; a.N = d; a.K = d; a.bias = F + lw.out_b; a.resid = w.row_x; a.out = w.row_xmid; a.ldc = d;
-            RUN(launch_gemm(EPI_BIAS_RESID, a, s));
-            RUN(launch_layernorm_f16(w.row_xmid, F + lw.ln2_g, F + lw.ln2_b, w.row_xn, 0, w.batch, d, s));
+            LAUNCH(launch_gemm(EPI_BIAS_RESID, a, s));
+            LAUNCH(launch_layernorm_f16(w.row_xmid, F + lw.ln2_g, F + lw.ln2_b, w.row_xn, 0, w.batch, d, s));
             a = GemmArgs{};
             a.A = w.row_xn; a.W = t->w16 + lw.fc_w; a.M = w.batch; a.m_pad = Bp; a.N = 4 * d; a.K = d; a.bias = F + lw.fc_b; a.out = w.row_h; a.out2 = w.row_hpre; a.ldc = 4 * d;
-            RUN(launch_gemm(EPI_BIAS_GELU_F16, a, s));
+            LAUNCH(launch_gemm(EPI_BIAS_GELU_F16, a, s));
             a = GemmArgs{};
             a.A = w.row_h; a.W = t->w16 + lw.proj_w; a.M = w.batch; a.m_pad = Bp; a.N = d; a.K = 4 * d; a.bias = F + lw.proj_b; a.resid = w.row_xmid; a.out = w.row_xout; a.ldc = d;
-            RUN(launch_gemm(EPI_BIAS_RESID, a, s));
+            LAUNCH(launch_gemm(EPI_BIAS_RESID, a, s));
             x = w.row_xout;
             *compact = true;
             break;
@@ -603,46 +656,47 @@ static int run_blocks(grip_tower* t, Workspace& w, resid_t* x0, int causal, cons
         GemmArgs a{};
         a.rot_rows = w.train;     // train-mode GEMMs may stagger their K walks by tile row (common.h)
         if (!fold) {
-            RUN(launch_layernorm_f16(x, F + lw.ln1_g, F + lw.ln1_b, w.xn, gf, w.M, d, s));
+            LAUNCH(launch_layernorm_f16(x, F + lw.ln1_g, F + lw.ln1_b, w.xn, gf, w.M, d, s));
             a.f32 = gf; a.w_exact = t->w_exact; a.A = w.xn; a.W = t->wop(t->split ? lw.in_wS : lw.in_w); a.M = w.M; a.m_pad = w.Mp; a.N = 3 * d; a.K = d; a.bias = F + lw.in_b; a.out = qkv; a.ldc = 3 * d;
-            RUN(launch_gemm(EPI_BIAS_F16, a, s));
-            if (t->split && attention_split_supported(w.S)) RUN(launch_attention_fwd_split((const float*)(const void*)qkv, att, w.batch, w.S, H, causal, s));
-            else if (f) RUN(launch_attention_fwd_f32((const float*)(const void*)qkv, (float*)(void*)att, w.batch, w.S, H, causal, s, t->split));
-            else RUN(launch_attention_fwd(qkv, att, w.batch, w.S, H, causal, s, w.Ps));
+            LAUNCH(launch_gemm(EPI_BIAS_F16, a, s));
+            if (t->split && attention_split_supported(w.S)) LAUNCH(launch_attention_fwd_split((const float*)(const void*)qkv, att, w.batch, w.S, H, causal, s));
+            else if (f) LAUNCH(launch_attention_fwd_f32((const float*)(const void*)qkv, (float*)(void*)att, w.batch, w.S, H, causal, s, t->split));
+            else LAUNCH(launch_attention_fwd(qkv, att, w.batch, w.S, H, causal, s, w.Ps));
         } else {
             a.A = x; a.W = t->w16 + lw.in_wG; a.M = w.M; a.m_pad = w.Mp; a.N = 3 * d; a.K = d; a.bias = F + lw.in_bb; a.colsum = F + lw.in_cs; a.rowstat = w.rowstat;
             if (parts_in && l > 0) { a.stat_in = w.stat_part; a.stat_parts = parts; }      // (block 0: the embedding kernel wrote rowstat)
             a.out = qkv; a.ldc = 3 * d;
-            RUN(launch_gemm(EPI_LNFOLD_F16, a, s));
-            RUN(launch_attention_fwd(qkv, att, w.batch, w.S, H, causal, s, w.Ps));
+            LAUNCH(launch_gemm(EPI_LNFOLD_F16, a, s));
+            LAUNCH(launch_attention_fwd(qkv, att, w.batch, w.S, H, causal, s, w.Ps));
         }
         a = GemmArgs{};
         a.rot_rows = w.train;
         a.f32 = gf; a.w_exact = t->w_exact; a.A = att; a.W = t->wop(t->split ? lw.out_wS : lw.out_w); a.M = w.M; a.m_pad = w.Mp; a.N = d; a.K = d; a.bias = F + lw.out_b; a.resid = x; a.out = x_mid; a.ldc = d;
         a.stat_part = fold ? w.stat_part : nullptr;
         a.resid_lo = hilo ? w.x_lo : nullptr;
-        RUN(launch_gemm(EPI_BIAS_RESID, a, s));
+        LAUNCH(launch_gemm(EPI_BIAS_RESID, a, s));
         a = GemmArgs{};
         a.rot_rows = w.train;
         if (!fold) {
-            RUN(launch_layernorm_f16(x_mid, F + lw.ln2_g, F + lw.ln2_b, w.xn, gf, w.M, d, s));
+            LAUNCH(launch_layernorm_f16(x_mid, F + lw.ln2_g, F + lw.ln2_b, w.xn, gf, w.M, d, s));
             a.f32 = gf; a.w_exact = t->w_exact; a.A = w.xn; a.W = t->wop(t->split ? lw.fc_wS : lw.fc_w); a.bias = F + lw.fc_b;
         } else {
             if (parts_in) { a.stat_in = w.stat_part; a.stat_parts = parts; }
-            else RUN(launch_ln_stats_finalize(w.stat_part, parts, w.rowstat, w.M, d, s));
+            else LAUNCH(launch_ln_stats_finalize(w.stat_part, parts, w.rowstat, w.M, d, s));
             a.A = x_mid; a.W = t->w16 + lw.fc_wG; a.bias = F + lw.fc_bb; a.colsum = F + lw.fc_cs; a.rowstat = w.rowstat;
         }
         a.M = w.M; a.m_pad = w.Mp; a.N = 4 * d; a.K = d; a.out = w.h; a.ldc = 4 * d;
         a.out2 = w.train ? w.hpre_l[(size_t)l] : nullptr;
-        RUN(launch_gemm(fold ? EPI_LNFOLD_GELU_F16 : EPI_BIAS_GELU_F16, a, s));
+        if (fold) LAUNCH(launch_gemm(EPI_LNFOLD_GELU_F16, a, s));      // (two sites: a launch budget names the call it stops before)
+        else LAUNCH(launch_gemm(EPI_BIAS_GELU_F16, a, s));
         a = GemmArgs{};
         a.rot_rows = w.train;
         a.f32 = gf; a.w_exact = t->w_exact; a.A = w.h; a.W = t->wop(t->split ? lw.proj_wS : lw.proj_w); a.M = w.M; a.m_pad = w.Mp; a.N = d; a.K = 4 * d; a.bias = F + lw.proj_b; a.resid = x_mid; a.out = x_out; a.ldc = d;
         a.stat_part = (!fold || (last && !hilo)) ? nullptr : w.stat_part;     // the final LayerNorm (CLS / EOT rows only) reads the stream itself
         a.resid_lo = hilo ? w.x_lo : nullptr;      // (the compensated form lives in the statistics-carrying epilogue: the last block's unread sums are its price)
         if (w.train && w.coop_ks > 1) { a.ksplit = w.coop_ks; a.coop_scratch = w.coop_scratch; a.coop_counter = w.coop_cnt; }
-        RUN(launch_gemm(EPI_BIAS_RESID, a, s));
-        if (fold && !last && !parts_in) RUN(launch_ln_stats_finalize(w.stat_part, parts, w.rowstat, w.M, d, s));
+        LAUNCH(launch_gemm(EPI_BIAS_RESID, a, s));
+        if (fold && !last && !parts_in) LAUNCH(launch_ln_stats_finalize(w.stat_part, parts, w.rowstat, w.M, d, s));
         x = x_out;
     }
     *x_final = x;
@@ -679,6 +733,7 @@ static void note_forward(grip_tower* t, void* workspace, int train, const Worksp
 
 extern "C" int grip_vit_forward_deep(grip_tower* t, const void* images, int images_f16, const float* prefix, int n_prefix, const float* deep, int n_deep,
                                      int batch, float* out_emb, void* workspace, size_t workspace_bytes, int flags, uint64_t* generation, void* stream) {
+    PassScope pass_scope;
     try {
         GRIP_REQUIRE(t && t->D.kind == 0, "vit_forward: not a vision tower%s", n_deep ? " (deep prompts are a vision-tower feature)" : "");
         GRIP_REQUIRE(n_deep >= 0 && n_deep <= t->D.layers - 1, "vit_forward_deep: n_deep = %d out of range: deep prompts replace the prompt rows entering blocks 1 .. n_deep, "
@@ -693,27 +748,28 @@ extern "C" int grip_vit_forward_deep(grip_tower* t, const void* images, int imag
         GRIP_REQUIRE(images && out_emb && (n_prefix == 0 || prefix), "vit_forward: null pointer");
         Workspace w;
         RUN(check_ws(t, batch, n_prefix, train, workspace, workspace_bytes, w));
+        if (g_launch_budget) t->pending.erase(workspace);      // a forward that may stop early leaves no pending state behind
         w.deep = n_deep ? deep : nullptr;
         w.n_deep = n_deep;
         hipStream_t s = (hipStream_t)stream;
         const grip_dims& D = t->D;
         const int d = D.width, G2 = D.seq0 - 1, f = t->f32;
         const float* F = t->w32;
-        RUN(launch_im2col(images, images_f16, w.patches, f, batch, D.resolution, D.patch, t->L.kpad, s));
+        LAUNCH(launch_im2col(images, images_f16, w.patches, f, batch, D.resolution, D.patch, t->L.kpad, s));
         GemmArgs a{};
         a.f32 = f; a.A = w.patches; a.W = t->wop(t->L.conv_w); a.M = batch * G2; a.m_pad = round_up64((int64_t)batch * G2, 256); a.N = d; a.K = t->L.kpad; a.out = w.patch_out; a.ldc = d;
-        RUN(launch_gemm(EPI_F32, a, s));
+        LAUNCH(launch_gemm(EPI_F32, a, s));
         resid_t* x0 = train ? w.x_in[0] : w.x;
         w.hilo = (flags & GRIP_FWD_STREAM_HILO) ? 1 : 0;
-        RUN(launch_vit_assemble_ln(w.patch_out, F + t->L.cls, (flags & GRIP_FWD_NO_POS_EMB) ? nullptr : F + t->L.pos, prefix, n_prefix, F + t->L.lnpre_g, F + t->L.lnpre_b, x0, f, (train && !train_fold(t)) ? nullptr : w.rowstat, batch, G2, d, s,
+        LAUNCH(launch_vit_assemble_ln(w.patch_out, F + t->L.cls, (flags & GRIP_FWD_NO_POS_EMB) ? nullptr : F + t->L.pos, prefix, n_prefix, F + t->L.lnpre_g, F + t->L.lnpre_b, x0, f, (train && !train_fold(t)) ? nullptr : w.rowstat, batch, G2, d, s,
                                    w.hilo ? w.x_lo : nullptr, per_image));
         resid_t* xf = nullptr;
         bool compact = false;
         RUN(run_blocks(t, w, x0, /*causal=*/0, nullptr, s, &xf, &compact));
-        RUN(launch_gather_ln_f16(xf, nullptr, compact ? 1 : w.S, F + t->L.lnpost_g, F + t->L.lnpost_b, w.cls16, f, batch, d, s));
+        LAUNCH(launch_gather_ln_f16(xf, nullptr, compact ? 1 : w.S, F + t->L.lnpost_g, F + t->L.lnpost_b, w.cls16, f, batch, d, s));
         a = GemmArgs{};
         a.f32 = f; a.A = w.cls16; a.W = t->wop(t->L.projT); a.M = batch; a.N = D.embed_dim; a.K = d; a.out = out_emb; a.ldc = D.embed_dim;
-        RUN(launch_gemm(EPI_F32, a, s));
+        LAUNCH(launch_gemm(EPI_F32, a, s));
         note_forward(t, workspace, train, w, nullptr, 0, generation, per_image != 0, n_deep);
         return GRIP_OK;
     } catch (...) { grip_set_error("vit_forward: exception"); return GRIP_ERR_ARG; }
@@ -727,6 +783,7 @@ extern "C" int grip_vit_forward(grip_tower* t, const void* images, int images_f1
 extern "C" int grip_text_forward_deep(grip_tower* t, const int32_t* token_ids, const int32_t* eot_index, const float* prefix,
                                       int n_prefix, int prefix_classes, const float* deep, int n_deep, int n_class, int seq_len, float* out_emb,
                                       void* workspace, size_t workspace_bytes, int flags, uint64_t* generation, void* stream) {
+    PassScope pass_scope;
     try {
         GRIP_REQUIRE(t && t->D.kind == 1, "text_forward: not a text tower%s", n_deep ? " (the vision tower's deep prompts go through grip_vit_forward_deep)" : "");
         GRIP_REQUIRE(n_deep >= 0 && n_deep <= t->D.layers - 1, "text_forward_deep: n_deep = %d out of range: deep prompts replace the context rows entering blocks 1 .. n_deep, "
@@ -742,6 +799,7 @@ extern "C" int grip_text_forward_deep(grip_tower* t, const int32_t* token_ids, c
         const int shared = (flags & GRIP_FWD_SHARED_PREFIX) && n_prefix > 0 && prefix_classes == 1 && !t->f32;
         Workspace w;
         RUN(check_ws(t, n_class, n_prefix, train, workspace, workspace_bytes, w, seq_len, shared));
+        if (g_launch_budget) t->pending.erase(workspace);      // a forward that may stop early leaves no pending state behind
         w.deep = n_deep ? deep : nullptr;
         w.n_deep = n_deep;
         w.deep_classes = n_deep ? prefix_classes : 1;
@@ -751,14 +809,14 @@ extern "C" int grip_text_forward_deep(grip_tower* t, const int32_t* token_ids, c
         const float* F = t->w32;
         resid_t* x0 = train ? w.x_in[0] : w.x;
         if (train && w.coop_cnt) GRIP_CHECK_HIP(hipMemsetAsync(w.coop_cnt, 0, w.coop_cnt_bytes, s));     // the tickets start at zero (and return to it)
-        RUN(launch_text_embed(token_ids, D.seq0, F + t->L.tok, (flags & GRIP_FWD_NO_POS_EMB) ? nullptr : F + t->L.pos, prefix, n_prefix, prefix_classes, x0, f, (train && !train_fold(t)) ? nullptr : w.rowstat, n_class, w.S, d, D.vocab, s, w.Ps));
+        LAUNCH(launch_text_embed(token_ids, D.seq0, F + t->L.tok, (flags & GRIP_FWD_NO_POS_EMB) ? nullptr : F + t->L.pos, prefix, n_prefix, prefix_classes, x0, f, (train && !train_fold(t)) ? nullptr : w.rowstat, n_class, w.S, d, D.vocab, s, w.Ps));
         resid_t* xf = nullptr;
         bool compact = false;
         RUN(run_blocks(t, w, x0, /*causal=*/1, eot_index, s, &xf, &compact));
-        RUN(launch_gather_ln_f16(xf, compact ? nullptr : eot_index, compact ? 1 : w.rs, F + t->L.lnpost_g, F + t->L.lnpost_b, w.cls16, f, n_class, d, s));
+        LAUNCH(launch_gather_ln_f16(xf, compact ? nullptr : eot_index, compact ? 1 : w.rs, F + t->L.lnpost_g, F + t->L.lnpost_b, w.cls16, f, n_class, d, s));
         GemmArgs a{};
         a.f32 = f; a.A = w.cls16; a.W = t->wop(t->L.projT); a.M = n_class; a.N = D.embed_dim; a.K = d; a.out = out_emb; a.ldc = D.embed_dim;
-        RUN(launch_gemm(EPI_F32, a, s));
+        LAUNCH(launch_gemm(EPI_F32, a, s));
         note_forward(t, workspace, train, w, eot_index, prefix_classes, generation, false, n_deep);
         return GRIP_OK;
     } catch (...) { grip_set_error("text_forward: exception"); return GRIP_ERR_ARG; }
@@ -1000,9 +1058,9 @@ static int run_blocks_backward(grip_tower* t, Workspace& w, int causal, const in
         const LayerW& lw = t->L.layer[(size_t)l];
         if (grad_deep && l + 1 <= w.n_deep) {
             if (t->D.kind == 0)
-                RUN(launch_vit_deep_grad(w.dx, w.dxh, w.scale, grad_deep + (size_t)l * w.P * d, w.batch, w.S, w.P, d, s));
+                LAUNCH(launch_vit_deep_grad(w.dx, w.dxh, w.scale, grad_deep + (size_t)l * w.P * d, w.batch, w.S, w.P, d, s));
             else
-                RUN(launch_text_deep_grad(w.dx, w.dxh, w.scale, grad_deep + (size_t)l * w.deep_classes * w.P * d, w.Ps ? 1 : w.batch, w.S, w.P, w.deep_classes, d, s));
+                LAUNCH(launch_text_deep_grad(w.dx, w.dxh, w.scale, grad_deep + (size_t)l * w.deep_classes * w.P * d, w.Ps ? 1 : w.batch, w.S, w.P, w.deep_classes, d, s));
         }
         if (l + 1 == t->D.layers && w.rows_last) {
             // the last block ran for the read rows only (run_blocks): enters with drow / drow_h = the gradient of those stream rows
@@ -1010,48 +1068,48 @@ static int run_blocks_backward(grip_tower* t, Workspace& w, int causal, const in
             const int64_t rpart = Bp * d;
             GemmArgs a{};
             a.A = w.drow_h; a.W = W + lw.proj_wT; a.M = w.batch; a.m_pad = Bp; a.N = 4 * d; a.K = d; a.aux = w.row_hpre; a.out = w.row_dh; a.ldc = 4 * d;
-            RUN(launch_gemm(EPI_GELUGRAD_F16, a, s));
+            LAUNCH(launch_gemm(EPI_GELUGRAD_F16, a, s));
             a = GemmArgs{};
             a.A = w.row_dh; a.W = W + lw.fc_wT; a.M = w.batch; a.m_pad = Bp; a.N = d; a.K = 4 * d; a.out = w.row_dln; a.ldc = d;
             a.ksplit = w.ks_row; a.split_stride = rpart;
-            RUN(launch_gemm(EPI_F32, a, s));
-            RUN(launch_ln_bwd_add(w.row_xmid, w.row_dln, w.ks_row, rpart, F + lw.ln2_g, w.drow, w.drow_h, w.batch, d, s));
+            LAUNCH(launch_gemm(EPI_F32, a, s));
+            LAUNCH(launch_ln_bwd_add(w.row_xmid, w.row_dln, w.ks_row, rpart, F + lw.ln2_g, w.drow, w.drow_h, w.batch, d, s));
             a = GemmArgs{};
             a.A = w.drow_h; a.W = W + lw.out_wT; a.M = w.batch; a.m_pad = Bp; a.N = d; a.K = d; a.out = w.row_datt; a.ldc = d;
-            RUN(launch_gemm(EPI_F16, a, s));
+            LAUNCH(launch_gemm(EPI_F16, a, s));
             // d(q, k, v) of every row from the read rows' d(attention output): rank-one in (q, dO) per head
-            RUN(launch_attention_row_bwd(w.qkv_l[(size_t)l], w.row_att, w.row_datt, read_rows, w.dqkv, w.batch, w.S, H, causal, s));
+            LAUNCH(launch_attention_row_bwd(w.qkv_l[(size_t)l], w.row_att, w.row_datt, read_rows, w.dqkv, w.batch, w.S, H, causal, s));
             a = GemmArgs{};
             a.rot_rows = 1;
             a.A = w.dqkv; a.W = W + lw.in_wT; a.M = w.M; a.m_pad = w.Mp; a.N = d; a.K = 3 * d; a.out = w.dln; a.ldc = d;
             a.ksplit = w.ks_in; a.split_stride = part;
-            RUN(launch_gemm(EPI_F32, a, s));
+            LAUNCH(launch_gemm(EPI_F32, a, s));
             // the stream gradient entering the block: drow at the read rows, zero elsewhere (no fill, no scatter)
-            RUN(launch_ln_bwd_init(w.x_in[(size_t)l], w.dln, w.ks_in, part, F + lw.ln1_g, w.drow, read_rows, w.S, w.dx, w.dxh, w.M, d, s));
+            LAUNCH(launch_ln_bwd_init(w.x_in[(size_t)l], w.dln, w.ks_in, part, F + lw.ln1_g, w.drow, read_rows, w.S, w.dx, w.dxh, w.M, d, s));
             continue;
         }
         GemmArgs a{};
         a.rot_rows = 1;           // (backward GEMMs: train mode by definition)
         // d(pre-activation) = (dx @ W_proj) * quickgelu'(h_pre)
         a.A = w.dxh; a.W = W + lw.proj_wT; a.M = w.M; a.m_pad = w.Mp; a.N = 4 * d; a.K = d; a.aux = w.hpre_l[(size_t)l]; a.out = w.dh; a.ldc = 4 * d;
-        RUN(launch_gemm(EPI_GELUGRAD_F16, a, s));
+        LAUNCH(launch_gemm(EPI_GELUGRAD_F16, a, s));
         a = GemmArgs{};
         a.rot_rows = 1;
         a.A = w.dh; a.W = W + lw.fc_wT; a.M = w.M; a.m_pad = w.Mp; a.N = d; a.K = 4 * d; a.out = w.dln; a.ldc = d;
         a.ksplit = w.ks_fc; a.split_stride = part;
-        RUN(launch_gemm(EPI_F32, a, s));
-        RUN(launch_ln_bwd_add(w.x_mid[(size_t)l], w.dln, w.ks_fc, part, F + lw.ln2_g, w.dx, w.dxh, w.M, d, s));
+        LAUNCH(launch_gemm(EPI_F32, a, s));
+        LAUNCH(launch_ln_bwd_add(w.x_mid[(size_t)l], w.dln, w.ks_fc, part, F + lw.ln2_g, w.dx, w.dxh, w.M, d, s));
         a = GemmArgs{};
         a.rot_rows = 1;
         a.A = w.dxh; a.W = W + lw.out_wT; a.M = w.M; a.m_pad = w.Mp; a.N = d; a.K = d; a.out = w.datt; a.ldc = d;
-        RUN(launch_gemm(EPI_F16, a, s));
-        RUN(launch_attention_bwd(w.qkv_l[(size_t)l], w.att_l[(size_t)l], w.datt, w.dqkv, w.batch, w.S, H, causal, s, w.Ps, w.kv_part));
+        LAUNCH(launch_gemm(EPI_F16, a, s));
+        LAUNCH(launch_attention_bwd(w.qkv_l[(size_t)l], w.att_l[(size_t)l], w.datt, w.dqkv, w.batch, w.S, H, causal, s, w.Ps, w.kv_part));
         a = GemmArgs{};
         a.rot_rows = 1;
         a.A = w.dqkv; a.W = W + lw.in_wT; a.M = w.M; a.m_pad = w.Mp; a.N = d; a.K = 3 * d; a.out = w.dln; a.ldc = d;
         a.ksplit = w.ks_in; a.split_stride = part;
-        RUN(launch_gemm(EPI_F32, a, s));
-        RUN(launch_ln_bwd_add(w.x_in[(size_t)l], w.dln, w.ks_in, part, F + lw.ln1_g, w.dx, w.dxh, w.M, d, s));
+        LAUNCH(launch_gemm(EPI_F32, a, s));
+        LAUNCH(launch_ln_bwd_add(w.x_in[(size_t)l], w.dln, w.ks_in, part, F + lw.ln1_g, w.dx, w.dxh, w.M, d, s));
     }
     return GRIP_OK;
 }
@@ -1060,15 +1118,17 @@ static int backward_head_of_tower(grip_tower* t, Workspace& w, const float* grad
     const grip_dims& D = t->D;
     const int d = D.width;
     // scale + f16 cast of dL/d(emb); d(ln output) = g @ proj^T  (W = proj [d, E] as stored: N = d, K = E)
-    RUN(launch_grad_scale_cast(grad_emb, w.gemb16, w.scale, w.batch * D.embed_dim, s));
+    LAUNCH(launch_grad_scale_cast(grad_emb, w.gemb16, w.scale, w.batch * D.embed_dim, s));
     GemmArgs a{};
     a.A = w.gemb16; a.W = t->w16 + t->L.proj; a.M = w.batch; a.N = d; a.K = D.embed_dim; a.out = w.dcls; a.ldc = d;
-    RUN(launch_gemm(EPI_F32, a, s));
-    if (w.rows_last)      // compact: the final stream exists for the read rows only (run_blocks)
-        return launch_ln_bwd_scatter(w.row_xout, w.dcls, nullptr, 1, t->w32 + t->L.lnpost_g, w.drow, w.drow_h, w.batch, d, s);
+    LAUNCH(launch_gemm(EPI_F32, a, s));
+    if (w.rows_last) {    // compact: the final stream exists for the read rows only (run_blocks)
+        LAUNCH(launch_ln_bwd_scatter(w.row_xout, w.dcls, nullptr, 1, t->w32 + t->L.lnpost_g, w.drow, w.drow_h, w.batch, d, s));
+        return GRIP_OK;
+    }
     // row of (sequence b, position index[b]): b * rs + index[b] in either layout (shared-prefix: Ps + b*(S-Ps) + index - Ps); every other row of the
     // stream gradient starts at zero (written by the same kernel)
-    RUN(launch_ln_bwd_scatter_fill(w.x_in[(size_t)D.layers], w.dcls, index, w.rs, w.Ps, t->w32 + t->L.lnpost_g, w.dx, w.dxh, w.batch, (int)w.M, d, s));
+    LAUNCH(launch_ln_bwd_scatter_fill(w.x_in[(size_t)D.layers], w.dcls, index, w.rs, w.Ps, t->w32 + t->L.lnpost_g, w.dx, w.dxh, w.batch, (int)w.M, d, s));
     return GRIP_OK;
 }
 
@@ -1101,6 +1161,7 @@ static int check_bwd(grip_tower* t, void* workspace, size_t workspace_bytes, uin
 
 extern "C" int grip_vit_backward_prefix(grip_tower* t, const float* grad_emb, const float* prefix, float* grad_prefix,
                                         void* workspace, size_t workspace_bytes, uint64_t generation, void* stream) {
+    PassScope pass_scope;
     try {
         GRIP_REQUIRE(t && t->D.kind == 0 && grad_emb && prefix && grad_prefix, "vit_backward_prefix: bad arguments");
         auto it = t->pending.find(workspace);
@@ -1116,15 +1177,16 @@ extern "C" int grip_vit_backward_prefix(grip_tower* t, const float* grad_emb, co
         RUN(backward_head_of_tower(t, w, grad_emb, nullptr, s));
         RUN(run_blocks_backward(t, w, 0, nullptr, s));
         if (st.per_image)     // one prompt per image: grad_prefix [batch, n_prefix, width], image b's rows only
-            RUN(launch_vit_prefix_grad_per_image(w.dx, prefix, t->w32 + t->L.lnpre_g, w.scale, grad_prefix, w.batch, w.S, w.P, t->D.width, s));
+            LAUNCH(launch_vit_prefix_grad_per_image(w.dx, prefix, t->w32 + t->L.lnpre_g, w.scale, grad_prefix, w.batch, w.S, w.P, t->D.width, s));
         else
-            RUN(launch_vit_prefix_grad(w.dx, prefix, t->w32 + t->L.lnpre_g, w.scale, grad_prefix, w.batch, w.S, w.P, t->D.width, s));
+            LAUNCH(launch_vit_prefix_grad(w.dx, prefix, t->w32 + t->L.lnpre_g, w.scale, grad_prefix, w.batch, w.S, w.P, t->D.width, s));
         return GRIP_OK;
     } catch (...) { grip_set_error("vit_backward_prefix: exception"); return GRIP_ERR_ARG; }
 }
 
 extern "C" int grip_vit_backward_deep(grip_tower* t, const float* grad_emb, const float* prefix, float* grad_prefix, float* grad_deep,
                                       void* workspace, size_t workspace_bytes, uint64_t generation, void* stream) {
+    PassScope pass_scope;
     try {
         GRIP_REQUIRE(t && t->D.kind == 0 && grad_emb && prefix && grad_prefix, "vit_backward_deep: bad arguments");
         auto it = t->pending.find(workspace);
@@ -1138,9 +1200,9 @@ extern "C" int grip_vit_backward_deep(grip_tower* t, const float* grad_emb, cons
         RUN(backward_head_of_tower(t, w, grad_emb, nullptr, s));
         RUN(run_blocks_backward(t, w, 0, nullptr, s, st.n_deep ? grad_deep : nullptr));
         if (st.per_image)
-            RUN(launch_vit_prefix_grad_per_image(w.dx, prefix, t->w32 + t->L.lnpre_g, w.scale, grad_prefix, w.batch, w.S, w.P, t->D.width, s));
+            LAUNCH(launch_vit_prefix_grad_per_image(w.dx, prefix, t->w32 + t->L.lnpre_g, w.scale, grad_prefix, w.batch, w.S, w.P, t->D.width, s));
         else
-            RUN(launch_vit_prefix_grad(w.dx, prefix, t->w32 + t->L.lnpre_g, w.scale, grad_prefix, w.batch, w.S, w.P, t->D.width, s));
+            LAUNCH(launch_vit_prefix_grad(w.dx, prefix, t->w32 + t->L.lnpre_g, w.scale, grad_prefix, w.batch, w.S, w.P, t->D.width, s));
         return GRIP_OK;
     } catch (...) { grip_set_error("vit_backward_deep: exception"); return GRIP_ERR_ARG; }
 }
@@ -1148,6 +1210,7 @@ extern "C" int grip_vit_backward_deep(grip_tower* t, const float* grad_emb, cons
 // (who: the entry point's name for the messages; grad_deep is only read when the forward ran with deep prompts)
 static int text_backward(const char* who, grip_tower* t, const float* grad_emb, float* grad_prefix, float* grad_deep,
                          void* workspace, size_t workspace_bytes, uint64_t generation, void* stream) {
+    PassScope pass_scope;
     GRIP_REQUIRE(t && t->D.kind == 1 && grad_emb && grad_prefix, "%s: bad arguments", who);
     grip_tower::TrainState st;
     RUN(check_bwd(t, workspace, workspace_bytes, generation, st));
@@ -1157,9 +1220,9 @@ static int text_backward(const char* who, grip_tower* t, const float* grad_emb, 
     RUN(backward_head_of_tower(t, w, grad_emb, st.eot, s));
     RUN(run_blocks_backward(t, w, 1, st.eot, s, st.n_deep ? grad_deep : nullptr));
     if (w.Ps)   // shared-prefix layout: every class's share already met in the shared rows (rows 1 .. P)
-        RUN(launch_text_prefix_grad(w.dx, w.scale, grad_prefix, 1, w.S, w.P, 1, t->D.width, s));
+        LAUNCH(launch_text_prefix_grad(w.dx, w.scale, grad_prefix, 1, w.S, w.P, 1, t->D.width, s));
     else
-        RUN(launch_text_prefix_grad(w.dx, w.scale, grad_prefix, w.batch, w.S, w.P, st.prefix_classes, t->D.width, s));
+        LAUNCH(launch_text_prefix_grad(w.dx, w.scale, grad_prefix, w.batch, w.S, w.P, st.prefix_classes, t->D.width, s));
     return GRIP_OK;
 }
 

@@ -206,7 +206,12 @@ _DEBUG_SIGS = {          # kernel-level test hooks (csrc/tower.hip), not part of
     "grip_debug_gather_rows": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     # the UPT mixer's workspace carve-up by name (csrc/mixer.hip), host only
     "grip_debug_upt_mixer_slot": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(ctypes.c_char_p), POINTER(c_int64), POINTER(c_int64)]),
+    # the towers' workspace carve-up by name and the launch budget of a tower pass (csrc/tower.hip), host only
+    "grip_debug_tower_slot": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(ctypes.c_char_p), POINTER(c_int), POINTER(c_int64),
+                                      POINTER(c_int64)]),
+    "grip_debug_launch_budget": (c_int, [c_int64]),
 }
+ERR_LAUNCH_BUDGET = 64      # GRIP_ERR_LAUNCH_BUDGET (include/grip_amd_debug.h)
 
 _lib = None
 
