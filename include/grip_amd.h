@@ -616,6 +616,33 @@ int grip_view_mode(const float* view_emb, const float* view_probs, int n, int v,
                    size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 9 additions) Marginal entropy of an image's confident views, and its gradient: the loss of a test-time prompt-tuning episode (tpt.TestTimeTuner;
+ * csrc/view_entropy.hip).  After TPT (Shu et al., "Test-time prompt tuning for zero-shot generalization in vision-language models", NeurIPS 2022).  What
+ * follows is THE MODEL OF THIS HEADER, NOT THE PAPER'S CODE.
+ * Image i has V views; x[p, :] are the logits of view p over c classes (logits [n v, c], image-major: the rows pseudolabels.MultiView.aggregate hands to
+ * the cosine head).
+ *   per view:   lse_p = max + logf(sum_c expf(x_pc - max)),   p_pc = expf(x_pc - lse_p),   H_p = -sum_c p_pc (x_pc - lse_p)   (every term >= 0; lane l of a
+ *               wave adds the classes l, l + 64, ... in ascending order, then the wave's fixed tree)
+ *   selection:  the `keep` views of smallest H_p; ties go to the lower view index; a view whose H_p is not finite ranks after every finite one, index
+ *               ascending.  The selection is a CONSTANT of the gradient.
+ *   marginal:   pbar_c = (sum_{p selected, ascending} p_pc) / keep
+ *   loss:       loss_i = -sum_c pbar_c logf(max(pbar_c, 2^-126))      (the floor of the Sinkhorn / soft-CE kernels)
+ *               loss = (1 / n) sum_i loss_i, added in ascending i and multiplied by 1.0f / (float)n
+ *   gradient:   g_c = -(logf(max(pbar_c, 2^-126)) + 1) / keep;  a selected view gets grad x_pj = (p_pj (g_j - sum_c p_pc g_c)) * (1.0f / (float)n), every
+ *               other view exactly +0.0 in every element.  Every element of grad_logits has one writer.
+ *   logits [n v, c]; loss [1]; grad_logits [n v, c], view_entropy_out [n, v] (H), selected_out [n, v] int32 (0 / 1) and mean_probs_out [n, c] (pbar) may
+ *   each be NULL.  All f32 / int32, element offsets 64-bit.  1 <= v <= 64, 1 <= keep <= v, 1 <= c <= 16000 (g lives in the LDS: the limit and the reason
+ *   of grip_candidate_ce), any n >= 1.  No output may alias logits or another output.  Logits that are not finite are the caller's duty.
+ * ONE launch for the per-image work (one workgroup per image, a wave per view, views beyond the wave count round-robin), no atomics, no scratch, no
+ * workspace.  n > 1 adds one single-workgroup launch for the mean over images: it re-adds the per-image loss terms from mean_probs_out in the image's own
+ * order (the same bits), or, when mean_probs_out is NULL, walks the images once more with every output off -- pass mean_probs_out when n is large.  Two
+ * calls are bit-equal.  H, selected, pbar and loss_i of an image depend on its [v, c] block and keep alone -- not on n, not on its place in the launch;
+ * n enters its gradient last, as the one multiplication above.  Refused with nothing written: a null logits / loss, n or c <= 0, v or keep out of range,
+ * c > 16000, an output that overlaps logits or another output. */
+int grip_view_entropy(const float* logits, int n, int v, int c, int keep, float* loss, float* grad_logits, float* view_entropy_out, int32_t* selected_out,
+                      float* mean_probs_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CLIP preprocessing of one decoded image: the `_transform` the reference applies per item on the host
  * (data/dataset.py:64-79 via clip.load's preprocess): Resize(n_px, BICUBIC) -> CenterCrop(n_px) -> ToTensor -> Normalize.
  * Bit-exact with Pillow's 8-bit bicubic resample; only the cropped rows / columns are produced.

@@ -1396,6 +1396,57 @@ def view_mode(view_emb, view_probs=None, rho=0.3, lam=4.0, lam_y=0.2, h2_floor=2
     return (mode, y, h2) if want_h2 else (mode, y)
 
 
+VIEW_ENTROPY_MAX_C = 16000      # csrc/view_entropy.hip: VE_MAXC (g lives in the LDS)
+
+
+def view_entropy(logits, views, keep, want_grad=True, want_entropy=False, want_selected=False, want_mean=False):
+    """(loss[, grad][, entropy][, selected][, mean]): the marginal entropy of every image's `keep` most confident views of include/grip_amd.h on the native
+    kernel (csrc/view_entropy.hip) -- logits f32 [n views, c], contiguous, on the GPU, image-major; loss 0-d f32, the mean over the n images; grad
+    [n views, c] (exactly +0.0 on the views that were not selected), entropy [n, views] (H_p), selected int32 [n, views] (0 / 1), mean [n, c] (pbar).
+    Everything is validated here, on the host, before the launch; bit-identical from call to call, and an image's entropies, selection and marginal do
+    not depend on n or on its place.  Meant for n = 1 (an episode) up to some hundreds of images (a chunk of views): the per-image work is one workgroup
+    per image, but the mean over n > 1 images is ONE workgroup that re-adds n c logarithms serially (27 us at 55 x 16 x 102) -- a pool-sized n would be one
+    CU's work; call it in chunks and average the losses on the host side of the graph instead.  No autograd (ViewEntropyFn)."""
+    if not torch.is_tensor(logits) or logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise native.GripError(f"view_entropy: logits must be a contiguous float32 [n views, c] tensor, got {getattr(logits, 'shape', type(logits))} "
+                               f"{getattr(logits, 'dtype', None)}")
+    require_gpu(logits.device)
+    for name, val in (("views", views), ("keep", keep)):
+        if isinstance(val, bool) or not isinstance(val, int):
+            raise native.GripError(f"view_entropy: {name} = {val!r} (an integer)")
+    rows, c = logits.shape
+    if not 1 <= views <= VIEW_MODE_MAX_VIEWS or not 1 <= keep <= views:
+        raise native.GripError(f"view_entropy: views = {views}, keep = {keep} (1 <= views <= {VIEW_MODE_MAX_VIEWS}, 1 <= keep <= views)")
+    if rows < 1 or rows % views or not 1 <= c <= VIEW_ENTROPY_MAX_C:
+        raise native.GripError(f"view_entropy: logits [{rows}, {c}] with {views} views (a positive multiple of views rows, 1 <= c <= {VIEW_ENTROPY_MAX_C})")
+    lg = logits.detach()
+    n, dev = rows // views, lg.device
+    loss = torch.zeros(1, dtype=torch.float32, device=dev)
+    grad = torch.empty_like(lg) if want_grad else None
+    ent = torch.empty(n, views, dtype=torch.float32, device=dev) if want_entropy else None
+    sel = torch.empty(n, views, dtype=torch.int32, device=dev) if want_selected else None
+    mean = torch.empty(n, c, dtype=torch.float32, device=dev) if want_mean or n > 1 else None      # (n > 1: the mean over images re-adds from it)
+    native.check(native.lib().grip_view_entropy(_ptr(lg), n, views, c, keep, _ptr(loss), _ptr(grad), _ptr(ent), _ptr(sel), _ptr(mean), _stream()))
+    out = (loss[0],) + tuple(t for t, want in ((grad, want_grad), (ent, want_entropy), (sel, want_selected), (mean, want_mean)) if want)
+    return out if len(out) > 1 else out[0]
+
+
+class ViewEntropyFn(torch.autograd.Function):
+    """logits -> the marginal-entropy loss of engine.view_entropy, native forward + backward (one kernel produces both; the gradient is scaled by the
+    incoming scalar in the backward, as WeightedCEFn's is).  apply(logits, views, keep)."""
+
+    @staticmethod
+    def forward(ctx, logits, views, keep):
+        loss, grad = view_entropy(logits.contiguous().float(), views, keep)
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None
+
+
 def leaderboard_scan(probs, pred, path_rank, k):
     """Host scan (exact, sequential).  probs [n,c] f32 CPU, pred [n] int32 CPU, path_rank [n] int64 CPU."""
     import numpy as np

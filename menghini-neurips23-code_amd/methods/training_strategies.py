@@ -35,6 +35,18 @@ def multi_view_from_config(config, keep=False):
                         keep_bytes=int(g("MV_CACHE_BYTES", 4 << 30)) if keep else 0)
 
 
+def tpt_settings_from_config(config):
+    """The keyword arguments of tpt.TestTimeTuner of a config's TPT_* settings; a bad value raises ValueError (the tuner's own checks, run here on a
+    sampler and a targets object, so that a config fails when the strategy is built and not at the first prediction)."""
+    from .. import tpt
+    g = lambda name, default: getattr(config, name, default)
+    kw = dict(views=g("TPT_VIEWS", 64), rho=float(g("TPT_RHO", 0.1)), lr=float(g("TPT_LR", 5e-3)), steps=g("TPT_STEPS", 1),
+              scale=tuple(g("TPT_SCALE", (0.08, 1.0))), ratio=tuple(g("TPT_RATIO", (3.0 / 4.0, 4.0 / 3.0))), flip=float(g("TPT_FLIP", 0.5)),
+              seed=int(g("TPT_SEED", 0)))
+    tpt.TestTimeTuner(None, None, **kw)      # (validates; holds no device memory)
+    return kw
+
+
 def make_scheduler(optimizer, config):
     """WarmupCosineSchedule stepped once per EPOCH (utils/schedulers.py:36-65 of the reference)."""
     warm, total = int(getattr(config, "WARMUP_EPOCHS", 0)), int(config.EPOCHS)
@@ -158,6 +170,23 @@ class TrainingStrategy:
         if bool(getattr(config, "MULTIVIEW_PSEUDOLABELS", False)) or self.mv_predict:
             self.multi_view = multi_view_from_config(config, keep=self.modality == "text")
         self.mv_passes = self.multi_view if bool(getattr(config, "MULTIVIEW_PSEUDOLABELS", False)) else None      # what the passes install
+        # TPT (textual strategies, default False; TPT_VIEWS 64, TPT_RHO 0.1, TPT_LR 5e-3, TPT_STEPS 1, TPT_SCALE (0.08, 1), TPT_RATIO (3/4, 4/3), TPT_FLIP 0.5:
+        # the paper's; TPT_SEED 0, TPT_VALIDATION False: untuned): `predict` -- and so test_predictions and evaluation -- classifies every item with a
+        # context tuned to it for the time of its prediction (tpt.TestTimeTuner: TPT_VIEWS views of the item through the frozen image tower, one
+        # episode of TPT_STEPS AdamW steps on the entropy of the mean prediction of its confident views, the row of view 0 under the tuned context);
+        # Tip, GDA and probe terms are added to that row from view 0's features as today.  The validation inside `train` runs every epoch and keeps
+        # the plain path unless TPT_VALIDATION is set.  The pseudolabel passes are untouched.  Visual and multimodal strategies ignore the switch:
+        # their image features move with the prompt, and an episode would be TPT_VIEWS tower backward passes.
+        self.tpt_settings, self._tpt, self._tpt_plain = None, None, False
+        if bool(getattr(config, "TPT", False)):
+            if self.modality != "text":
+                log.info(f"TPT is ignored by the {self.modality} strategies: their image features move with the prompt (textual strategies only)")
+            else:
+                if self.mv_predict:
+                    raise ValueError("TPT and MV_PREDICT are two answers to the same question (how to classify an item from its views): set one of them")
+                if bool(getattr(config, "CLIP_ADAPTER", False)):
+                    raise ValueError("TPT and CLIP_ADAPTER: an episode would have to adapt the view features (this composition is not built): set one of them")
+                self.tpt_settings = tpt_settings_from_config(config)
         self.declare_custom_encoder()
         self.initialize_prompts_parameters()
 
@@ -595,9 +624,15 @@ class TrainingStrategy:
         are dropped again (:285-294)."""
         ids = torch.tensor([self.label_to_idx[c] for c in classes], device=self.device)
         outs = []
+        tuner = self.test_time_tuner(classes)      # None unless TPT is on (and this is not the plain validation of `train`)
         for batch in self._loader(data, False):
             img = batch[0].to(self.device)
-            if self.mv_predict:       # MV_PREDICT: the mode of each item's views under the current model stands in for its single embedding
+            if tuner is not None:     # TPT: every item's row comes from a context tuned on its own views; view 0's features feed the heads below
+                view_features = tuner.encode_views(img, list(batch[-1]))      # (the item names: last in a batch, with or without labels)
+                image_features = view_features[:, 0].contiguous()
+                logits = tuner.predict_rows(view_features)
+                text_features = None
+            elif self.mv_predict:     # MV_PREDICT: the mode of each item's views under the current model stands in for its single embedding
                 views = self.multi_view.make_views(img.float().contiguous(), list(batch[-1]))      # (the item names: last in a batch, with or without labels)
                 view_features, text_features = self.features(views, classes)
                 image_features = self.multi_view.aggregate(view_features.detach().float().view(img.shape[0], self.multi_view.views, -1), text_features.detach(),
@@ -606,7 +641,8 @@ class TrainingStrategy:
                 image_features, text_features = self.features(img, classes)
             if self.adapter is not None:      # CLIP_ADAPTER: the features are adapted before the head (row by row: the batching changes no bit)
                 image_features = self.adapter(image_features)
-            logits, _, am, _ = cosine_head(image_features, text_features, self.scale(), want_probs=False)
+            if tuner is None:
+                logits, _, am, _ = cosine_head(image_features, text_features, self.scale(), want_probs=False)
             if self.tip is not None:      # TIP_ADAPTER: the cache term of the iteration's training set
                 logits = self._add_cache_term(image_features, logits, classes)
             if self.gda is not None:      # GDA_HEAD: the discriminant term of the iteration's training set
@@ -617,6 +653,17 @@ class TrainingStrategy:
         logits = torch.cat(outs) if outs else torch.empty(0, len(classes), device=self.device)
         logits = gdist.gather_in_dataset_order(logits, len(data), int(self.config.BATCH_SIZE))
         return ids[logits.argmax(1)].cpu(), logits.cpu()
+
+    def test_time_tuner(self, classes):
+        """The tpt.TestTimeTuner of the current model over `classes`, or None: TPT off, or the plain validation of `train`.  One tuner per model
+        (define_model makes a new one stale); it owns its optimizer."""
+        if self.tpt_settings is None or self._tpt_plain:
+            return None
+        from ..tpt import TestTimeTuner
+        if self._tpt is None or self._tpt.model is not self.model:
+            self._tpt = TestTimeTuner(self.model, self.clip_model, **self.tpt_settings)
+        self.model.classes = classes
+        return self._tpt
 
     def _run_validation(self, val_data, only_seen=False):
         classes = self.seen_classes if only_seen and self.val_unseen_files is None else self.classes
@@ -631,7 +678,11 @@ class TrainingStrategy:
         best_acc, best_prompt = -1.0, None
         for epoch in range(int(self.config.EPOCHS)):
             loss, acc = self._train_epoch(loader, only_seen=only_seen, epoch=epoch)
-            val_acc = self._run_validation(val_data, only_seen=only_seen) if val_data is not None and len(val_data) else acc
+            self._tpt_plain = not bool(getattr(self.config, "TPT_VALIDATION", False))      # (an episode per validation item every epoch: only on request)
+            try:
+                val_acc = self._run_validation(val_data, only_seen=only_seen) if val_data is not None and len(val_data) else acc
+            finally:
+                self._tpt_plain = False
             log.info(f"epoch {epoch}: loss {loss:.4f} train acc {acc:.3f} val acc {val_acc:.3f}")
             if val_acc > best_acc:
                 best_acc, best_prompt = val_acc, self.prompt_snapshot()

@@ -1264,6 +1264,26 @@ def candidates():
     return _CANDIDATES[-1] if _CANDIDATES else None
 
 
+def view_boxes(sampler, views, names, H, W):
+    """int32 [len(names) * views, 5] of (top, left, height, width, flip), image-major: view 0 of every image is the whole image, un-flipped; view p >= 1 is
+    the box `sampler` (an augment.ViewSampler) draws for (seed, base name, epoch 0, view p) -- an item's boxes depend on its name alone, not on its batch
+    or the rank.  Shared by MultiView and tpt.TestTimeTuner."""
+    out = np.empty((len(names), views, 5), dtype=np.int32)
+    out[:, 0] = (0, 0, H, W, 0)
+    for i, name in enumerate(names):
+        base = os.path.basename(str(name))
+        for p in range(1, views):
+            out[i, p] = sampler.box(base, 0, H, W, view=p)
+    return out.reshape(-1, 5)
+
+
+def make_views(sampler, views, images, names):
+    """images [B, 3, H, H] f32 on the GPU -> their views [B * views, 3, H, H] of view_boxes, image-major (view 0 is a bit-exact copy)."""
+    from . import augment
+    B, _, H, W = images.shape
+    return augment.views(images, view_boxes(sampler, views, names, H, W), rows=np.repeat(np.arange(B, dtype=np.int64), views), n_px=H)
+
+
 class MultiView:
     """Settings of the multi-view pseudolabel pass (off unless installed by multi_view(); after MTA, Zanella & Ben Ayed, CVPR 2024 -- the model of
     include/grip_amd.h, not the paper's code): every pool image is encoded `views` times -- view 0 the image as it is, views 1 .. V - 1 boxes of an
@@ -1299,19 +1319,11 @@ class MultiView:
     def boxes(self, names, H, W):
         """int32 [len(names) * V, 5] of (top, left, height, width, flip), image-major: view 0 of every image is the whole image, un-flipped; view p >= 1
         is the sampler's box of (seed, base name, epoch 0, view p)."""
-        out = np.empty((len(names), self.views, 5), dtype=np.int32)
-        out[:, 0] = (0, 0, H, W, 0)
-        for i, name in enumerate(names):
-            base = os.path.basename(str(name))
-            for p in range(1, self.views):
-                out[i, p] = self.sampler.box(base, 0, H, W, view=p)
-        return out.reshape(-1, 5)
+        return view_boxes(self.sampler, self.views, names, H, W)
 
     def make_views(self, images, names):
         """images [B, 3, H, H] f32 on the GPU -> their views [B * V, 3, H, H], image-major (view 0 is a bit-exact copy)."""
-        from . import augment
-        B, _, H, W = images.shape
-        return augment.views(images, self.boxes(names, H, W), rows=np.repeat(np.arange(B, dtype=np.int64), self.views), n_px=H)
+        return make_views(self.sampler, self.views, images, names)
 
     @torch.no_grad()
     def encode_views(self, tower, images, paths, chunk=880, prefix=None, deep=None):

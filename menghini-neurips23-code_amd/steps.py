@@ -9,7 +9,7 @@ import torch
 
 from . import dist as gdist
 from . import engine
-from .engine import CandidateCEFn, CosineHeadFn, SoftCEFn, WeightedCEFn
+from .engine import CandidateCEFn, CosineHeadFn, SoftCEFn, ViewEntropyFn, WeightedCEFn
 
 
 def fpl_row_weights(is_pseudo, gamma_seen=1.0, gamma_pseudo=1.0):
@@ -74,15 +74,37 @@ class CandidateTargets:
         return ("candidates", self.mask.data_ptr(), tuple(self.mask.shape), self.col_map.data_ptr())
 
 
+class ViewEntropyTargets:
+    """What a test-time episode step (tpt.TestTimeTuner) hands over as `soft=`: no targets at all -- the logits' rows are `views` views per image,
+    image-major, and the loss is the entropy of the mean prediction of every image's `keep` most confident views (engine.view_entropy); step_loss
+    dispatches on the type.  labels, row_weight and soft_row are not read."""
+
+    matrix = None      # no per-pool-row buffer: a graphed step keeps no soft_row
+
+    def __init__(self, views, keep):
+        for name, val in (("views", views), ("keep", keep)):
+            if isinstance(val, bool) or not isinstance(val, int):
+                raise ValueError(f"ViewEntropyTargets: {name} = {val!r} (an integer)")
+        if not 1 <= views <= engine.VIEW_MODE_MAX_VIEWS or not 1 <= keep <= views:
+            raise ValueError(f"ViewEntropyTargets: views = {views}, keep = {keep} (1 <= views <= {engine.VIEW_MODE_MAX_VIEWS}, 1 <= keep <= views)")
+        self.views, self.keep = views, keep
+
+    def key(self):
+        """What a captured graph depends on."""
+        return ("view_entropy", self.views, self.keep)
+
+
 def step_loss(logits, labels, row_weight, soft=None, soft_row=None):
     """The loss of a prompt step: WeightedCEFn, exactly as before, without `soft`; SoftCEFn on the rows of soft.matrix that soft_row names with a
-    SoftTargets; CandidateCEFn on the rows of soft.mask that soft_row names with a CandidateTargets."""
+    SoftTargets; CandidateCEFn on the rows of soft.mask that soft_row names with a CandidateTargets; ViewEntropyFn with a ViewEntropyTargets."""
     if soft is None:
         return WeightedCEFn.apply(logits, labels, row_weight)
     if isinstance(soft, CandidateTargets):
         if soft_row is None:
             raise ValueError("a step with candidate sets needs the batch's soft_row (the mask row of every batch row, -1 for a hard row)")
         return CandidateCEFn.apply(logits, labels, row_weight, soft.mask, soft_row, soft.col_map)
+    if isinstance(soft, ViewEntropyTargets):
+        return ViewEntropyFn.apply(logits, soft.views, soft.keep)
     if soft.matrix is None:
         return SoftCEFn.apply(logits, labels, row_weight, None, None, None, soft.temperature, soft.smoothing)
     if soft_row is None:
