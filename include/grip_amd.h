@@ -643,6 +643,54 @@ int grip_view_entropy(const float* logits, int n, int v, int c, int keep, float*
                       float* mean_probs_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 9 additions) Test-time streaming cache over the items of one `predict` call (tda.StreamCache; csrc/stream_cache.hip).  After TDA (Karmanov et al.,
+ * "Efficient test-time adaptation of vision-language models", the training-free dynamic adapter, CVPR 2024): no tower pass, no backward, any modality.
+ * What follows is THE MODEL OF THIS HEADER, NOT THE PAPER'S CODE (one queue rule for both polarities, the stream is the whole call in dataset order,
+ * nothing survives the call).
+ * base_logits [n, c] (whatever the heads produced) and img_emb [n, e] (NOT normalised: 1 / |f| = 1.0f / sqrtf(sum f^2) multiplies the score, the rule of
+ * grip_cache_head_forward), both in stream order.
+ *   per item:   lse_i = max + logf(sum_c expf(x_ic - max)),  p_ic = expf(x_ic - lse_i),  H_i = -sum_c p_ic (x_ic - lse_i)   (grip_view_entropy's statements:
+ *               lane l of a wave adds the classes l, l + 64, ... ascending, then the wave's fixed tree);  pred_i = the FIRST arg-max of x_i (a row in which
+ *               nothing compares greater than -inf, e.g. a row of NaNs: 0);  Hn_i = H_i / L in f32 with L = (float)log((double)c), and 0 for c = 1;
+ *               negbits_i: bit (y mod 32) of word y / 32 is set iff mask_lo < p_iy < mask_hi  ([n, ceil(c / 32)] int32 holding the 32 bits, the layout of
+ *               grip_candidate_select's mask; bits >= c are zero).
+ *   queues:     every class has a positive queue of capacity pos_cap and a negative one of capacity neg_cap (0: no negative queue); item i goes to the
+ *               queues of class pred_i.  The negative queue admits only items with ent_lo < Hn_i < ent_hi.  A queue that is not full takes the item.  A
+ *               full queue takes it only if H_i is STRICTLY smaller than H of the resident with the largest (H, index); that resident leaves.  The
+ *               comparisons are on the f32 H written to entropy_out.  A non-finite H_i is never admitted.
+ *   score:      item i is scored AFTER its own admission, against the residents of that moment:
+ *                 out[i, y] = base[i, y] + pos_alpha Spos - neg_alpha Sneg,
+ *                 Spos = sum_{j in Pos_i, pred_j = y} a(i, j; pos_beta),   Sneg = sum_{j in Neg_i, bit y of negbits_j} a(i, j; neg_beta),
+ *                 a(i, j; beta) = expf(-(beta (1 - s_ij))),  s_ij = ((f_i . f_j) (1 / |f_i|)) (1 / |f_j|), the dot product one f32 MFMA chain over e.
+ *               Each sum is one f32 chain over its live keys in ascending j starting from 0; the positive term is added first, each as a rounded product
+ *               and a rounded sum.  A sum that is 0 (no live key, or every term underflowed) leaves the element alone: such a column is base, bit for bit.
+ * The queue updates depend on the base logits alone, so the stream is evaluated in two calls, and the result is the sequential algorithm's item for item:
+ * grip_stream_cache_plan (three launches: a wave per row; a wave per (class, polarity) that walks pred in order -- no atomic, no cross-workgroup wait; a
+ * deterministic compaction) writes
+ *   entropy_out [n] f32 (H), pred_out [n] int32, negbits_out [n, ceil(c / 32)] int32,
+ *   pos_leave / neg_leave [n] int32: item j sat in the queue during the stream positions [j, leave_j): leave_j = j means never admitted, INT32_MAX still
+ *   resident at the end, else the index of the item that evicted it,
+ *   pos_key / neg_key [n] int32: the ever-admitted items, ascending (the first counts_out[0] / counts_out[1] entries; the rest is not written),
+ *   counts_out [2] int32 on the device.
+ * grip_stream_cache_head (a memset and three launches) is the f32-MFMA main loop of the cache head with the key rows gathered from img_emb through the
+ * key lists (no key copy); item i sums exactly the keys j with j <= i < leave_j, tested in the epilogue; the [n, m] affinities are never written; one
+ * writer per element, no atomics.  A row tile stops at the last key tile that holds a key j <= its last row.  It reads the two counts ON THE DEVICE: no
+ * launch geometry depends on them and a stream costs no host read.  negbits, neg_leave and neg_key all NULL: no negative term.  out must not overlap an input.
+ * The workspace holds the reciprocal norms and the two [n, c] sums (grip_stream_cache_head_workspace; the plan's is 0 bytes today and may be NULL).
+ * Two calls are bit-equal.  CAUSALITY: rows 0 .. k-1 of every output of a run on the first k items are bit-equal to rows 0 .. k-1 of the run on all n,
+ * but for leave (an item still resident after k items may leave later).  e a multiple of 4 up to 1 024, img_emb 16-byte aligned; any c >= 1,
+ * 1 <= n <= 2^30; pos_cap 1 .. 16, neg_cap 0 .. 16; the windows finite with lo <= hi; alpha and beta finite.  The worst case m = n (entropies strictly
+ * descending within one class) is served.  Out-of-range arguments are refused with nothing written; the _workspace calls need no device. */
+int grip_stream_cache_plan_workspace(int n, int c, size_t* bytes);
+int grip_stream_cache_plan(const float* base_logits, int n, int c, int pos_cap, int neg_cap, float ent_lo, float ent_hi, float mask_lo, float mask_hi,
+                           float* entropy_out, int32_t* pred_out, int32_t* pos_leave, int32_t* neg_leave, int32_t* negbits_out, int32_t* pos_key,
+                           int32_t* neg_key, int32_t* counts_out, void* workspace, size_t workspace_bytes, void* stream);
+int grip_stream_cache_head_workspace(int n, int c, int e, size_t* bytes);
+int grip_stream_cache_head(const float* base_logits, const float* img_emb, const int32_t* pred, const int32_t* negbits, const int32_t* pos_leave,
+                           const int32_t* neg_leave, const int32_t* pos_key, const int32_t* neg_key, const int32_t* counts, float pos_alpha, float pos_beta,
+                           float neg_alpha, float neg_beta, int n, int c, int e, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CLIP preprocessing of one decoded image: the `_transform` the reference applies per item on the host
  * (data/dataset.py:64-79 via clip.load's preprocess): Resize(n_px, BICUBIC) -> CenterCrop(n_px) -> ToTensor -> Normalize.
  * Bit-exact with Pillow's 8-bit bicubic resample; only the cropped rows / columns are produced.

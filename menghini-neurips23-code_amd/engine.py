@@ -1447,6 +1447,109 @@ class ViewEntropyFn(torch.autograd.Function):
         return grad * g, None, None
 
 
+STREAM_CACHE_MAX_CAP = 16       # csrc/stream_cache.hip: SC_MAX_CAP (a queue lives in 16 lanes)
+STREAM_CACHE_MAX_E = 1024       # csrc/stream_cache.hip: SC_MAX_E
+STREAM_CACHE_MAX_N = 1 << 30    # csrc/stream_cache.hip: SC_MAX_N
+# the paper's ImageNet settings AS RECALLED, untuned here (tda.StreamCache documents them)
+STREAM_CACHE_DEFAULTS = dict(pos_cap=3, neg_cap=2, pos_alpha=2.0, pos_beta=5.0, neg_alpha=0.117, neg_beta=1.0, neg_entropy=(0.2, 0.5), neg_mask=(0.03, 1.0))
+STREAM_CACHE_PLAN_FIELDS = ("entropy", "pred", "negbits", "pos_leave", "neg_leave", "pos_key", "neg_key", "counts")
+
+
+def check_stream_cache_settings(who, pos_cap=3, neg_cap=2, pos_alpha=2.0, pos_beta=5.0, neg_alpha=0.117, neg_beta=1.0, neg_entropy=(0.2, 0.5),
+                                neg_mask=(0.03, 1.0)):
+    """The settings of a streaming cache as (pos_cap, neg_cap, pos_alpha, pos_beta, neg_alpha, neg_beta, (ent_lo, ent_hi), (mask_lo, mask_hi)), validated
+    on the host (no device needed); a bad value raises GripError."""
+    for name, val, lo in (("pos_cap", pos_cap, 1), ("neg_cap", neg_cap, 0)):
+        if isinstance(val, bool) or not isinstance(val, int) or not lo <= val <= STREAM_CACHE_MAX_CAP:
+            raise native.GripError(f"{who}: {name} = {val!r} (an integer in {lo} .. {STREAM_CACHE_MAX_CAP})")
+    scal = [_probe_scalar(who, name, val, positive=False)
+            for name, val in (("pos_alpha", pos_alpha), ("pos_beta", pos_beta), ("neg_alpha", neg_alpha), ("neg_beta", neg_beta))]
+    wins = []
+    for name, val in (("neg_entropy", neg_entropy), ("neg_mask", neg_mask)):
+        try:
+            lo, hi = (float(v) for v in val)
+        except (TypeError, ValueError):
+            raise native.GripError(f"{who}: {name} = {val!r} (a pair (lo, hi))") from None
+        if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+            raise native.GripError(f"{who}: {name} = ({lo:g}, {hi:g}) (finite, lo <= hi)")
+        wins.append((lo, hi))
+    return (pos_cap, neg_cap, *scal, *wins)
+
+
+def _stream_cache_logits(who, base_logits):
+    if not torch.is_tensor(base_logits) or base_logits.dim() != 2 or base_logits.dtype != torch.float32 or not base_logits.is_contiguous():
+        raise native.GripError(f"{who}: base_logits must be a contiguous float32 [n, c] tensor, got {getattr(base_logits, 'shape', type(base_logits))} "
+                               f"{getattr(base_logits, 'dtype', None)}")
+    require_gpu(base_logits.device)
+    n, c = base_logits.shape
+    if not 1 <= n <= STREAM_CACHE_MAX_N or c < 1:
+        raise native.GripError(f"{who}: base_logits [{n}, {c}] (1 <= n <= 2^30, c >= 1)")
+    return base_logits.detach(), n, c
+
+
+def stream_cache_plan(base_logits, pos_cap=3, neg_cap=2, neg_entropy=(0.2, 0.5), neg_mask=(0.03, 1.0)):
+    """The queue history of a stream of base logits f32 [n, c] (dataset order) under the model of include/grip_amd.h, on the native kernels
+    (csrc/stream_cache.hip: a row launch, a scan launch with a wave per (class, polarity), a compaction) -- a dict of device tensors: entropy f32 [n] (H),
+    pred int32 [n], negbits int32 [n, ceil(c / 32)], pos_leave / neg_leave int32 [n] (item j sat in its queue during [j, leave_j); leave_j == j: never
+    admitted, INT32_MAX: resident at the end), pos_key / neg_key int32 [n] (the ever-admitted items, ascending; only the first counts[0] / counts[1]
+    entries are written) and counts int32 [2].  Nothing is read back to the host.  Validated here before the launches; bit-identical from call to call."""
+    x, n, c = _stream_cache_logits("stream_cache_plan", base_logits)
+    pos_cap, neg_cap, _, _, _, _, (ent_lo, ent_hi), (mask_lo, mask_hi) = check_stream_cache_settings("stream_cache_plan", pos_cap=pos_cap, neg_cap=neg_cap,
+                                                                                                  neg_entropy=neg_entropy, neg_mask=neg_mask)
+    dev = x.device
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    plan = dict(entropy=torch.empty(n, dtype=torch.float32, device=dev), pred=i32(n), negbits=i32(n, (c + 31) // 32), pos_leave=i32(n), neg_leave=i32(n),
+                pos_key=i32(n), neg_key=i32(n), counts=i32(2))
+    lib = native.lib()
+    ws = _gda_workspace(lib.grip_stream_cache_plan_workspace, (n, c), dev)      # (0 bytes today)
+    native.check(lib.grip_stream_cache_plan(_ptr(x), n, c, pos_cap, neg_cap, ent_lo, ent_hi, mask_lo, mask_hi, _ptr(plan["entropy"]), _ptr(plan["pred"]),
+                                            _ptr(plan["pos_leave"]), _ptr(plan["neg_leave"]), _ptr(plan["negbits"]), _ptr(plan["pos_key"]),
+                                            _ptr(plan["neg_key"]), _ptr(plan["counts"]), _ptr(ws) if ws.numel() else c_void_p(0), ws.numel(), _stream()))
+    return plan
+
+
+def stream_cache_head(base_logits, img_emb, plan, pos_alpha=2.0, pos_beta=5.0, neg_alpha=0.117, neg_beta=1.0, negative=True):
+    """The adapted logits f32 [n, c] of a stream: base_logits plus the positive and minus the negative cache term of include/grip_amd.h, every item
+    against exactly the keys that sat in a queue when it was scored (plan: stream_cache_plan's dict for the SAME base_logits), on the native f32-MFMA kernel
+    (csrc/stream_cache.hip).  img_emb f32 [n, e], not normalised.  negative = False leaves the negative term out (the plan of neg_cap = 0 holds none
+    anyway).  No host read: the key counts are read on the device."""
+    x, n, c = _stream_cache_logits("stream_cache_head", base_logits)
+    if not torch.is_tensor(img_emb) or img_emb.dim() != 2 or img_emb.dtype != torch.float32 or img_emb.shape[0] != n or img_emb.device != x.device:
+        raise native.GripError(f"stream_cache_head: img_emb must be a float32 [{n}, e] tensor on {x.device}, got {getattr(img_emb, 'shape', type(img_emb))} "
+                               f"{getattr(img_emb, 'dtype', None)}")
+    e = img_emb.shape[1]
+    if e < 4 or e % 4 or e > STREAM_CACHE_MAX_E:
+        raise native.GripError(f"stream_cache_head: e = {e} (a multiple of 4 up to {STREAM_CACHE_MAX_E})")
+    f = img_emb.detach().contiguous()
+    _, _, pos_alpha, pos_beta, neg_alpha, neg_beta, _, _ = check_stream_cache_settings("stream_cache_head", pos_alpha=pos_alpha, pos_beta=pos_beta,
+                                                                                       neg_alpha=neg_alpha, neg_beta=neg_beta)
+    shapes = dict(pred=(n,), negbits=(n, (c + 31) // 32), pos_leave=(n,), neg_leave=(n,), pos_key=(n,), neg_key=(n,), counts=(2,))
+    if not isinstance(plan, dict):
+        raise native.GripError(f"stream_cache_head: plan must be the dict of stream_cache_plan, got {type(plan)}")
+    for name, shape in shapes.items():
+        t = plan.get(name)
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != shape or t.device != x.device or not t.is_contiguous():
+            raise native.GripError(f"stream_cache_head: plan[{name!r}] must be a contiguous int32 {list(shape)} tensor on {x.device}, got "
+                                   f"{getattr(t, 'shape', type(t))} {getattr(t, 'dtype', None)}")
+    lib = native.lib()
+    ws = _gda_workspace(lib.grip_stream_cache_head_workspace, (n, c, e), x.device)
+    out = torch.empty_like(x)
+    neg = (lambda name: _ptr(plan[name])) if negative else (lambda name: c_void_p(0))
+    native.check(lib.grip_stream_cache_head(_ptr(x), _ptr(f), _ptr(plan["pred"]), neg("negbits"), _ptr(plan["pos_leave"]), neg("neg_leave"),
+                                            _ptr(plan["pos_key"]), neg("neg_key"), _ptr(plan["counts"]), pos_alpha, pos_beta, neg_alpha, neg_beta, n, c, e,
+                                            _ptr(out), _ptr(ws), ws.numel(), _stream()))
+    return out
+
+
+def stream_cache(base_logits, img_emb, pos_cap=3, neg_cap=2, pos_alpha=2.0, pos_beta=5.0, neg_alpha=0.117, neg_beta=1.0, neg_entropy=(0.2, 0.5),
+                 neg_mask=(0.03, 1.0)):
+    """(logits, plan): the whole stream -- stream_cache_plan, then stream_cache_head on its plan (the negative term off when neg_cap = 0).  The rows are
+    the sequential item-by-item algorithm's; rows 0 .. k-1 do not depend on the items from k on."""
+    plan = stream_cache_plan(base_logits, pos_cap=pos_cap, neg_cap=neg_cap, neg_entropy=neg_entropy, neg_mask=neg_mask)
+    return stream_cache_head(base_logits, img_emb, plan, pos_alpha=pos_alpha, pos_beta=pos_beta, neg_alpha=neg_alpha, neg_beta=neg_beta,
+                             negative=neg_cap > 0), plan
+
+
 def leaderboard_scan(probs, pred, path_rank, k):
     """Host scan (exact, sequential).  probs [n,c] f32 CPU, pred [n] int32 CPU, path_rank [n] int64 CPU."""
     import numpy as np

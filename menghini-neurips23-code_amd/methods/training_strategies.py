@@ -47,6 +47,17 @@ def tpt_settings_from_config(config):
     return kw
 
 
+def stream_cache_from_config(config):
+    """The tda.StreamCache of a config's TDA_* settings (TDA_POS_CAP 3, TDA_NEG_CAP 2, TDA_POS_ALPHA 2.0, TDA_POS_BETA 5.0, TDA_NEG_ALPHA 0.117,
+    TDA_NEG_BETA 1.0, TDA_NEG_ENTROPY (0.2, 0.5), TDA_NEG_MASK (0.03, 1.0): the paper's as recalled, untuned here); a bad value raises ValueError when
+    the strategy is built."""
+    from .. import tda
+    g = lambda name, default: getattr(config, name, default)
+    return tda.StreamCache(pos_cap=g("TDA_POS_CAP", 3), neg_cap=g("TDA_NEG_CAP", 2), pos_alpha=g("TDA_POS_ALPHA", 2.0), pos_beta=g("TDA_POS_BETA", 5.0),
+                           neg_alpha=g("TDA_NEG_ALPHA", 0.117), neg_beta=g("TDA_NEG_BETA", 1.0), neg_entropy=g("TDA_NEG_ENTROPY", (0.2, 0.5)),
+                           neg_mask=g("TDA_NEG_MASK", (0.03, 1.0)))
+
+
 def make_scheduler(optimizer, config):
     """WarmupCosineSchedule stepped once per EPOCH (utils/schedulers.py:36-65 of the reference)."""
     warm, total = int(getattr(config, "WARMUP_EPOCHS", 0)), int(config.EPOCHS)
@@ -187,6 +198,15 @@ class TrainingStrategy:
                 if bool(getattr(config, "CLIP_ADAPTER", False)):
                     raise ValueError("TPT and CLIP_ADAPTER: an episode would have to adapt the view features (this composition is not built): set one of them")
                 self.tpt_settings = tpt_settings_from_config(config)
+        # TDA (all modalities and paradigms, default False; the TDA_* settings of stream_cache_from_config; TDA_VALIDATION False): `predict` -- and so
+        # test_predictions and evaluation -- runs the items' logits and image features, gathered in dataset order, through a test-time streaming cache
+        # (tda.StreamCache: per-class queues of the lowest-entropy items seen so far, every item scored against the queues of its moment).  No tower
+        # pass: it sees only what the heads produced, so it composes with Tip, GDA, probe, adapter, MV_PREDICT and TPT.  Every rank runs the same
+        # stream over the whole gathered set.  The validation inside `train` keeps the plain path unless TDA_VALIDATION is set.  The pseudolabel
+        # passes are untouched.
+        self.tda, self._tda_plain = None, False
+        if bool(getattr(config, "TDA", False)):
+            self.tda = stream_cache_from_config(config)
         self.declare_custom_encoder()
         self.initialize_prompts_parameters()
 
@@ -625,6 +645,7 @@ class TrainingStrategy:
         ids = torch.tensor([self.label_to_idx[c] for c in classes], device=self.device)
         outs = []
         tuner = self.test_time_tuner(classes)      # None unless TPT is on (and this is not the plain validation of `train`)
+        cache, feats = (None if self._tda_plain else self.tda), []      # TDA: the features of every batch are kept for the stream below
         for batch in self._loader(data, False):
             img = batch[0].to(self.device)
             if tuner is not None:     # TPT: every item's row comes from a context tuned on its own views; view 0's features feed the heads below
@@ -650,8 +671,13 @@ class TrainingStrategy:
             if self.probe is not None:    # LINEAR_PROBE: the trained residual of the iteration's training set
                 logits = self._add_probe_term(image_features, logits, classes)
             outs.append(logits)
+            if cache is not None:
+                feats.append(image_features.detach().float())      # what the head terms saw
         logits = torch.cat(outs) if outs else torch.empty(0, len(classes), device=self.device)
         logits = gdist.gather_in_dataset_order(logits, len(data), int(self.config.BATCH_SIZE))
+        if cache is not None and feats:     # TDA: one stream over the whole set, in dataset order, the same on every rank
+            emb = gdist.gather_in_dataset_order(torch.cat(feats), len(data), int(self.config.BATCH_SIZE))
+            logits = cache(logits, emb)
         return ids[logits.argmax(1)].cpu(), logits.cpu()
 
     def test_time_tuner(self, classes):
@@ -679,10 +705,11 @@ class TrainingStrategy:
         for epoch in range(int(self.config.EPOCHS)):
             loss, acc = self._train_epoch(loader, only_seen=only_seen, epoch=epoch)
             self._tpt_plain = not bool(getattr(self.config, "TPT_VALIDATION", False))      # (an episode per validation item every epoch: only on request)
+            self._tda_plain = not bool(getattr(self.config, "TDA_VALIDATION", False))
             try:
                 val_acc = self._run_validation(val_data, only_seen=only_seen) if val_data is not None and len(val_data) else acc
             finally:
-                self._tpt_plain = False
+                self._tpt_plain = self._tda_plain = False
             log.info(f"epoch {epoch}: loss {loss:.4f} train acc {acc:.3f} val acc {val_acc:.3f}")
             if val_acc > best_acc:
                 best_acc, best_prompt = val_acc, self.prompt_snapshot()

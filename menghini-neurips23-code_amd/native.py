@@ -137,6 +137,13 @@ _SIGS = {
                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     # (ABI 9 additions) marginal entropy of an image's confident views and its gradient: the loss of a test-time prompt-tuning episode (csrc/view_entropy.hip)
     "grip_view_entropy": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # (ABI 9 additions) test-time streaming cache: the queue scan of a stream of base logits and the interval-masked cache head (csrc/stream_cache.hip)
+    "grip_stream_cache_plan_workspace": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "grip_stream_cache_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "grip_stream_cache_head_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "grip_stream_cache_head": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float,
+                                       c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "grip_preprocess_image": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                       c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "grip_preprocess_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
